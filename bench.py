@@ -7,7 +7,13 @@ preStepCallback's rolling-shutter table rebuild from the IMU stream (main_AriaKi
 damp + Schur-eliminate landmarks + factor + solve the reduced system, box-plus, cost pass, and the
 LM accept/reject (+ rescaled / sub-step attempts when the step is bad), as driven by vb_optimize.
 
-    python bench.py [--gpus N --steps K --warmup W --config C]
+    python bench.py [--gpus N --steps K --warmup W --config C] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: generate the problem, load it, W warmup
+iterations, K timed iterations, the result line.  --dump-outputs DIR also writes what the timed optimize
+call left (the variables of every kind and its summary) as DIR/<name>.npy.  --full adds the measurements
+that take runs of their own: the event-timed roofline pass of one kernel family, the banded flop count,
+the CPU baseline, and with --precision mixed the first-step deviation from fp64.
 
 N > 1 runs under torch.distributed (one rank per GPU): landmarks are sharded in time-banded
 ranges, every rank linearizes/eliminates its shard, the partial reduced systems are summed on
@@ -188,6 +194,36 @@ def banded_contributions(p, device, rs_device, precision):
             os.environ["VIBA_ND_LEAF"] = prev
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(e, summary, directory: str) -> dict:
+    """What a caller of the timed optimize call receives, as float64 DIR/<name>.npy: the variables of every
+    kind after the last timed iteration (vars_<kind>.npy, rows as vb_get_vars) and the call's summary
+    (summary.npy: initial cost, final cost, iterations, rescaled iterations, troubled sequences, largest
+    troubled sequence).  At most DUMP_BUDGET_BYTES in all: a larger output keeps a fixed, seeded sample of
+    every kind's rows (the same rows from run to run).  Returns {name: shape}."""
+    import numpy as np
+    from visual_inertial_bundle_adjustment_amd.kinds import NUM_VAR_KINDS, VAR_NAMES
+    arrays = {f"vars_{VAR_NAMES[k]}": e.get_vars(k) for k in range(NUM_VAR_KINDS) if e.nvars[k]}
+    arrays["summary"] = np.array([summary.initial_cost, summary.final_cost, summary.num_iterations,
+                                  summary.num_rescaled, summary.num_troubled_seqs, summary.largest_troubled_seq],
+                                 dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = 0.95 * DUMP_BUDGET_BYTES / total
+        rng = np.random.default_rng(0)
+        for name in sorted(arrays):
+            a = arrays[name]
+            if a.ndim == 2 and a.shape[0] > 1:
+                rows = np.sort(rng.choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+                arrays[name] = a[rows]
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def spawn_ranks(n: int) -> int:
     """`bench.py --gpus N` without a launcher: run this script under torch.distributed.run with N ranks
     (one per GPU, RCCL) as a child process, before anything here touches a GPU, and return its exit code
@@ -209,7 +245,14 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed optimize call left (the variables of every "
+                         "kind, its summary) as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the event-timed roofline pass "
+                         "(--profile-family), the banded flop count, the CPU baseline, and with --precision mixed "
+                         "the first-step deviation from fp64.  Without it the options that tune those have no effect")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--profile-family", type=int, default=KF_GEMM,
                     help="kernel family whose launches a separate pass after the timed one event-times for the "
                          "roofline (-1: none)")
@@ -236,6 +279,8 @@ def main():
                     help="ark_vi_ba --recompute-preint: every iteration re-preintegrates every inertial factor "
                          "from the IMU stream on the device (preint.hip)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed loop and its result line only
+        args.no_cpu_baseline, args.no_banded_count, args.profile_family = True, True, -1
     if args.solver != "direct" and args.profile_family == KF_GEMM:
         args.profile_family = KF_SYMV  # no fan-in without the factorization: the PCG product instead
 
@@ -248,6 +293,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
+        if args.dump_outputs:
+            log("[bench] --dump-outputs writes the single-GPU run's outputs; ignored with more than one rank")
         from visual_inertial_bundle_adjustment_amd.distributed import run_sharded
         return run_sharded(args, rank, world, local)
 
@@ -259,7 +306,7 @@ def main():
     log(f"[bench] config {args.config}: {p.summary()} (generated in {time.perf_counter() - t:.1f}s)")
     t = time.perf_counter()
     tolerance = None
-    if args.precision == "mixed":
+    if args.precision == "mixed" and args.full:
         tolerance = mixed_vs_fp64(p, local, args.rs_tables == "device")
         log(f"[bench] mixed vs fp64, first LM step: {tolerance}")
     e = HipEngine(imu_calib_options=p.imu_calib_options, device=local, precision=args.precision)
@@ -299,6 +346,13 @@ def main():
     log(f"[bench] timed {iters} its in {elapsed:.3f}s, cost {s.initial_cost:.6g} -> {s.final_cost:.6g}; "
         f"last it: lin {ph.linearize_ms:.2f} schur {ph.schur_ms:.2f} factor {ph.factor_ms:.2f} "
         f"solve {ph.solve_ms:.2f} step {ph.step_ms:.2f} cost {ph.cost_ms:.2f} rs-tables {ph.rs_update_ms:.3f} ms")
+    if iters != args.steps:
+        # only the damping bound can end the loop early (the convergence stops are disabled above)
+        log(f"[bench] the timed loop ran {iters} iterations, not the {args.steps} of --steps")
+        return 1
+    if args.dump_outputs:  # before the profiled pass below moves the variables on
+        shapes = dump_outputs(e, s, args.dump_outputs)
+        log(f"[bench] outputs of the timed optimize call written to {args.dump_outputs}: {shapes}")
     # the roofline's kernel timing: a separate pass of the same binary with the profiled family's launches
     # event-timed one by one, on the same multi-stream schedule as the timed pass: a launch can share the
     # chip with the other stream's, so the roofline divides by the family's busy time (the union of its
