@@ -769,15 +769,16 @@ __device__ __forceinline__ void group_finish(const Dev& d, double lambda, int mo
 // 818 / 794 / 862 / 1045 / 1041 us (LDS per workgroup sets the occupancy); fp32 records 609 / 564 / 550 /
 // 543 / 632 us
 // Round 6 (r06ad): the point Jacobian's pieces (planes 2..7, never read here) are not staged, and the chunk
-// takes as many records as the same loads and buffer hold: fp64 33 pieces x 31 records in 4 loads per thread
-// (24 x 36 before), fp32 records 17 x 45 in 3 (32 x 18).
+// takes as many records as the same loads and buffer hold: fp64 31 records of 33 pieces in 4 loads per thread
+// (4 * 256 / 33 = 31; 24 records of 36 pieces before), fp32 records 45 records of 17 pieces in 3 loads
+// (3 * 256 / 17 = 45; 32 records of 18 pieces before).
 constexpr int kRecPieces = kJPlanes / kRecV;                       // 16 B pieces per record (36 / 18)
 constexpr int kGrpSkip = 8 / kRecV - 1;                            // pieces after the first holding planes < 8 only
 constexpr int kGrpPieces = kRecPieces - kGrpSkip;                  // staged pieces per record (33 / 17)
 constexpr int kGrpPlanes = kGrpPieces * kRecV;                     // staged planes per record
 constexpr int kGrpShift = kGrpSkip * kRecV;                        // record plane p >= 8 is staged plane p - kGrpShift
 constexpr int kGrpLoads = VIBA_MIXED ? 3 : 4;                      // global_load_lds per thread per chunk
-constexpr int kGrpChunk = kGrpLoads * 256 / kGrpPieces;            // records per chunk (31 / 45)
+constexpr int kGrpChunk = kGrpLoads * 256 / kGrpPieces;            // records per chunk (fp64 4 * 256 / 33 = 31, fp32 records 3 * 256 / 17 = 45)
 constexpr int kGrpStage = kGrpLoads * 256 * kRecV;                 // rec_t per buffer (tail pieces land past the chunk)
 constexpr int kGrpIdx = 1024;                                      // observation indices per window
 static_assert(kJA % kRecV == 0 && kJB % kRecV == 0, "record regions in whole 16 B pieces");
