@@ -334,11 +334,31 @@ int vb_reduced_layout(vb_handle h, int32_t* kinds, int32_t* handles, int64_t* of
  * (+1e-9 below 1e-9, else x2, :530-545).  Block q lists variables [block_start[q], block_start[q + 1])
  * of (kinds, handles); its joint covariance (the matching rows and columns of H^-1, H the damped
  * Hessian) is written column-major, sum of tangent dims squared, after the previous block's.  Reduced
- * variables only: landmark points are eliminated by this engine (VB_E_UNSUPPORTED), constant variables
+ * variables only: landmark points are eliminated by this engine (VB_E_UNSUPPORTED here;
+ * vb_compute_point_covariances answers them), constant variables
  * have no covariance (VB_E_ARG).  One reduced solve per column on the device.  used_damping (may be
  * NULL) receives the damping of the factor that succeeded.  Invalidates the LM state of the handle. */
 int vb_compute_covariances(vb_handle h, double damping, int64_t n_blocks, const int64_t* block_start,
                            const int32_t* kinds, const int32_t* handles, double* out, double* used_damping);
+/* The landmark points of Optimizer::computeJointCovariances / computeCovariances (lib/small_thing/
+ * Optimizer.cpp:503-697), which vb_compute_covariances refuses: request q is the joint covariance of point
+ * points[q] (a VB_VAR_POINT handle) followed by the reduced variables [with_start[q], with_start[q + 1]) of
+ * (with_kinds, with_handles); with_start == NULL: no request has extra variables.  Block q is written
+ * column-major after block q - 1, ordered [point (3), variables ...] -- the block [(VB_VAR_POINT, p), ...] of
+ * computeJointCovariances; with no extra variables it is the point's 3 x 3 marginal.  Same prologue and
+ * damping rule as vb_compute_covariances (used_damping as there); then from the selected inversion Z = S^-1
+ * of the reduced factor, the point's Cholesky factor L_p and its eliminated panel Y_p = L_p^-1 W_p:
+ *   Sigma_pp = L_p^-T (I + Y_p Z_cc Y_p^T) L_p^-1,  Sigma_px = -L_p^-T Y_p Z_c,x,  Sigma_xx' = Z_x,x'
+ * (c: the reduced rows of the panel's columns), one wave or workgroup per point on the device.
+ * VB_E_ARG: a point handle out of range, a constant point, an extra variable that is a point, constant, or
+ * does not observe the point.  VB_E_UNSUPPORTED on a landmark shard or a partitioned rank.  n == 0
+ * succeeds.  Invalidates the LM state of the handle. */
+int vb_compute_point_covariances(vb_handle h, double damping, int64_t n, const int32_t* points,
+                                 const int64_t* with_start, const int32_t* with_kinds,
+                                 const int32_t* with_handles, double* out, double* used_damping);
+/* host time [ms] of the phases of the last vb_compute_point_covariances: the prologue (linearization,
+ * elimination, factorization), the selected inversion, and the part after it (requests, kernel, read-back) */
+int vb_point_covariance_times(vb_handle h, double ms[3]);
 /* test fault injection: in iteration `iteration` (0-based, -1 = off) of the next vb_optimize calls the
  * model cost reduction is negated, which takes the reference's "quadratic model failing numerically"
  * branch (Optimizer.cpp:835-854: damping *= dampingAdjustOnFail, the step is kept) */

@@ -1,6 +1,45 @@
 // Covariances (≙ Optimizer::computeJointCovariances / computeCovariances, Optimizer.cpp:503-697): the
-// selected inversion of the tile factor (selinv.hip) and the per-column solves of off-pattern blocks.
+// selected inversion of the tile factor (selinv.hip), the per-column solves of off-pattern blocks, and the
+// covariances of landmark points from the inversion and the elimination's panels (pointcov.hip).
 #include "host.hpp"
+
+// (kind, handle) -> reduced variable
+static std::unordered_map<int64_t, int32_t> reducedIndex(vb_handle h) {
+  std::unordered_map<int64_t, int32_t> rvOf;
+  for (size_t i = 0; i < h->rvKind.size(); i++) rvOf[((int64_t)h->rvKind[i] << 32) | (uint32_t)h->rvHandle[i]] = (int32_t)i;
+  return rvOf;
+}
+
+// The prologue of both covariance calls (Optimizer.cpp:503-545): linearize at the current variables without
+// touching the cost cache, eliminate the points at the damping, assemble and factor the reduced system
+// (initDirectSolverData + factor); while the factor breaks down the damping is raised (+1e-9 below 1e-9,
+// else x2).  *used = the damping of the factor that succeeded.  Leaves Vchol, the Y panels and the factor.
+static int covariancePrologue(vb_handle h, double damping, double* used) {
+  Dev& d = h->d;
+  double lam = damping;
+  for (int attempt = 0;; attempt++) {
+    if (int rc = vb_linearize(h, 0, 0, nullptr)) return rc;
+    HIPCHK(hipMemsetAsync(d.err, 0, sizeof(int32_t), h->st));
+    launch_landmark(d, lam, 0, d.lmB, d.lmE, h->st);
+    HIPCHK(hipMemsetAsync(d.rhs, 0, (size_t)d.nT * TS * sizeof(double), h->st));
+    launch_schur(d, lam, 1, h->st);
+    h->factorOnly = true;  // (the fused forward solve would run on a stale right-hand side)
+    const int frc = factorReduced(h);
+    h->factorOnly = false;
+    if (frc) return frc;
+    int32_t e = 0;
+    HIPCHK(hipMemcpyAsync(&e, d.err, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    if (!(e & (2 | 8))) {
+      if (int rc = checkErr(h)) return rc;
+      break;
+    }
+    if (attempt > 200) return fail(VB_E_NUMERIC, "covariances: factor keeps breaking down");
+    lam = lam < 1e-9 ? lam + 1e-9 : lam * 2.0;
+  }
+  *used = lam;
+  return 0;
+}
 
 extern "C" {
 int selectedInversion(vb_handle h) {
@@ -58,9 +97,7 @@ int vb_compute_covariances(vb_handle h, double damping, int64_t n_blocks, const 
   if (n_blocks < 0 || (n_blocks > 0 && (!block_start || !kinds || !handles || !out)))
     return fail(VB_E_ARG, "vb_compute_covariances: null argument");
   if (!h->sch[0].built) return fail(VB_E_STATE, "no factorization schedule");
-  // (kind, handle) -> reduced variable
-  std::unordered_map<int64_t, int32_t> rvOf;
-  for (size_t i = 0; i < h->rvKind.size(); i++) rvOf[((int64_t)h->rvKind[i] << 32) | (uint32_t)h->rvHandle[i]] = (int32_t)i;
+  const std::unordered_map<int64_t, int32_t> rvOf = reducedIndex(h);
   const int64_t nv = n_blocks ? block_start[n_blocks] : 0;
   std::vector<int32_t> rv(nv);
   for (int64_t q = 0; q < n_blocks; q++)
@@ -72,28 +109,8 @@ int vb_compute_covariances(vb_handle h, double damping, int64_t n_blocks, const 
     rv[i] = it->second;
   }
   Dev& d = h->d;
-  // initDirectSolverData + factor, retried with more damping while the factor breaks down
   double lam = damping;
-  for (int attempt = 0;; attempt++) {
-    if (int rc = vb_linearize(h, 0, 0, nullptr)) return rc;
-    HIPCHK(hipMemsetAsync(d.err, 0, sizeof(int32_t), h->st));
-    launch_landmark(d, lam, 0, d.lmB, d.lmE, h->st);
-    HIPCHK(hipMemsetAsync(d.rhs, 0, (size_t)d.nT * TS * sizeof(double), h->st));
-    launch_schur(d, lam, 1, h->st);
-    h->factorOnly = true;  // (the fused forward solve would run on a stale right-hand side)
-    const int frc = factorReduced(h);
-    h->factorOnly = false;
-    if (frc) return frc;
-    int32_t e = 0;
-    HIPCHK(hipMemcpyAsync(&e, d.err, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    if (!(e & (2 | 8))) {
-      if (int rc = checkErr(h)) return rc;
-      break;
-    }
-    if (attempt > 200) return fail(VB_E_NUMERIC, "covariances: factor keeps breaking down");
-    lam = lam < 1e-9 ? lam + 1e-9 : lam * 2.0;
-  }
+  if (int rc = covariancePrologue(h, damping, &lam)) return rc;
   if (used_damping) *used_damping = lam;
   // Every element (row ra, column rb of the padded reduced order) of a block whose tiles lie on the
   // factor's pattern comes from the selected inversion.  That covers SingleSessionProblem::
@@ -179,5 +196,103 @@ int vb_compute_covariances(vb_handle h, double damping, int64_t n_blocks, const 
   }
   h->linearized = false, h->factored = false;
   return checkErr(h);
+}
+
+int vb_compute_point_covariances(vb_handle h, double damping, int64_t n, const int32_t* points,
+                                 const int64_t* with_start, const int32_t* with_kinds, const int32_t* with_handles,
+                                 double* out, double* used_damping) {
+  if (!h || !h->finalized) return fail(VB_E_STATE, "vb_compute_point_covariances before vb_finalize");
+  if (h->partSet || h->sharded) return fail(VB_E_UNSUPPORTED, "covariances run on a single handle");
+  if (n < 0 || (n > 0 && (!points || !out))) return fail(VB_E_ARG, "vb_compute_point_covariances: null argument");
+  const int64_t nw = (n && with_start) ? with_start[n] : 0;
+  if (nw > 0 && (!with_kinds || !with_handles)) return fail(VB_E_ARG, "vb_compute_point_covariances: null argument");
+  Dev& d = h->d;
+  h->pointCovMs[0] = h->pointCovMs[1] = h->pointCovMs[2] = 0.0;
+  if (n == 0) {
+    if (used_damping) *used_damping = damping;
+    return 0;
+  }
+  if (!h->sch[0].built) return fail(VB_E_STATE, "no factorization schedule");
+  // the requests: landmark of every point, panel columns of the extra variables
+  std::vector<int64_t> lmY(d.nPts + 1);
+  HIPCHK(hipMemcpy(lmY.data(), d.lmY, lmY.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  std::vector<int32_t> reqLm(n), xPc;
+  std::vector<int64_t> xStart(n + 1, 0), outOff(n + 1, 0);
+  for (int64_t q = 0; q < n; q++) {
+    if (points[q] < 0 || points[q] >= d.nvar[VB_VAR_POINT]) return fail(VB_E_ARG, "point handle out of range");
+    if (h->lmOfPoint[points[q]] < 0) return fail(VB_E_ARG, "covariance of a constant point");
+    reqLm[q] = h->lmOfPoint[points[q]];
+  }
+  if (nw > 0) {
+    std::vector<int64_t> lmBlk(d.nPts + 1);
+    HIPCHK(hipMemcpy(lmBlk.data(), d.lmBlk, lmBlk.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    std::vector<int32_t> blkRed(lmBlk.back()), blkCol(lmBlk.back());
+    if (!blkRed.empty()) {
+      HIPCHK(hipMemcpy(blkRed.data(), d.blkRed, blkRed.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(blkCol.data(), d.blkCol, blkCol.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    const std::unordered_map<int64_t, int32_t> rvOf = reducedIndex(h);
+    for (int64_t q = 0; q < n; q++) {
+      if (with_start[q + 1] < with_start[q] || with_start[q] < 0) return fail(VB_E_ARG, "with_start must be non-decreasing");
+      const int64_t l = reqLm[q];
+      for (int64_t i = with_start[q]; i < with_start[q + 1]; i++) {
+        if (with_kinds[i] == VB_VAR_POINT) return fail(VB_E_ARG, "the extra variables of a point covariance are reduced variables");
+        auto it = rvOf.find(((int64_t)with_kinds[i] << 32) | (uint32_t)with_handles[i]);
+        if (it == rvOf.end()) return fail(VB_E_ARG, "covariance of a constant or unknown variable");
+        // the landmark's blocks are sorted by reduced id
+        const auto b0 = blkRed.begin() + lmBlk[l], b1 = blkRed.begin() + lmBlk[l + 1];
+        const auto b = std::lower_bound(b0, b1, it->second);
+        if (b == b1 || *b != it->second) return fail(VB_E_ARG, "the variable does not observe the point");
+        for (int j = 0; j < h->rvDim[it->second]; j++) xPc.push_back(blkCol[b - blkRed.begin()] + j);
+      }
+      xStart[q + 1] = (int64_t)xPc.size();
+    }
+  }
+  std::vector<int32_t> items, big;
+  for (int64_t q = 0; q < n; q++) {
+    const int64_t N = 3 + xStart[q + 1] - xStart[q];
+    outOff[q + 1] = outOff[q] + N * N;
+    const int64_t l = reqLm[q];
+    ((lmY[l + 1] - lmY[l]) / 3 <= kLmSmallCols ? items : big).push_back((int32_t)q);
+  }
+  const int64_t nSmall = (int64_t)items.size(), nBig = (int64_t)big.size();
+  items.insert(items.end(), big.begin(), big.end());
+
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  const auto t0 = now();
+  double lam = damping;
+  if (int rc = covariancePrologue(h, damping, &lam)) return rc;
+  if (used_damping) *used_damping = lam;
+  h->linearized = false, h->factored = false;  // the inversion consumes the factor
+  const auto t1 = now();
+  if (d.nT > 0)
+    if (int rc = selectedInversion(h)) return rc;
+  const auto t2 = now();
+  int32_t *itemsD = nullptr, *reqLmD = nullptr, *xPcD = nullptr;
+  int64_t *xStartD = nullptr, *outOffD = nullptr;
+  double* outD = nullptr;
+  int rc = 0;
+  if (upload(&itemsD, items) || upload(&reqLmD, reqLm) || upload(&xPcD, xPc) || upload(&xStartD, xStart) ||
+      upload(&outOffD, outOff) || hipMalloc((void**)&outD, (size_t)outOff[n] * sizeof(double)) != hipSuccess) {
+    rc = fail(VB_E_HIP, "point covariances: device allocation");
+  } else {
+    launch_pointcov(d, itemsD, nSmall, nBig, reqLmD, xStartD, xPcD, outOffD, outD, h->st);
+    if (hipMemcpyAsync(out, outD, (size_t)outOff[n] * sizeof(double), hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+        hipStreamSynchronize(h->st) != hipSuccess)
+      rc = fail(VB_E_HIP, "point covariances: kernel failure");
+  }
+  for (void* p : {(void*)itemsD, (void*)reqLmD, (void*)xPcD, (void*)xStartD, (void*)outOffD, (void*)outD})
+    if (p) (void)hipFree(p);
+  if (rc) return rc;
+  const auto t3 = now();
+  h->pointCovMs[0] = ms(t0, t1), h->pointCovMs[1] = ms(t1, t2), h->pointCovMs[2] = ms(t2, t3);
+  return checkErr(h);
+}
+
+int vb_point_covariance_times(vb_handle h, double ms[3]) {
+  if (!h || !ms) return fail(VB_E_ARG, "vb_point_covariance_times: null argument");
+  std::copy(h->pointCovMs, h->pointCovMs + 3, ms);
+  return 0;
 }
 }  // extern "C"

@@ -86,6 +86,8 @@ void launch_selinv_level(double* tiles, const int32_t* tileIdx, int32_t nT, cons
                          const int32_t* uItems, int nU, const int32_t* zItems, int nZ, const int32_t* dItems, int nD,
                          hipStream_t st);
 void launch_gather(const double* src, const int64_t* idx, int64_t n, double* out, hipStream_t st);
+void launch_pointcov(const Dev& d, const int32_t* items, int64_t nSmall, int64_t nBig, const int32_t* reqLm,
+                     const int64_t* xStart, const int32_t* xPc, const int64_t* outOff, double* out, hipStream_t st);
 void launch_zero_tiles(double* tiles, const int32_t* list, int64_t n, hipStream_t st);
 void launch_lp_cast(const double* in, float* out, int64_t n, hipStream_t st);
 void launch_lp_uncast(const float* in, double* out, int64_t n, hipStream_t st);
@@ -367,6 +369,8 @@ struct vb_handle_s {
   double *dinv = nullptr, *yvec = nullptr, *rhsWork = nullptr, *linv = nullptr;
   // a factorization without a solve to follow (vb_compute_covariances): no fused forward solve, eager
   bool factorOnly = false;
+  // host time [ms] of the last vb_compute_point_covariances: prologue, selected inversion, the rest
+  double pointCovMs[3] = {0.0, 0.0, 0.0};
   // tiles the linearization clears (single handle): every tile but those one Schur item stores whole
   int32_t* clearTilesD = nullptr;
   int64_t nClear = 0;

@@ -317,6 +317,43 @@ class CEngineBase:
             o += s * s
         return covs, used.value
 
+    def compute_point_covariances(self, points, with_vars=None, damping: float = 1e-5):
+        """Covariances of landmark points (vb_compute_point_covariances): request q is point points[q]
+        jointly with the reduced variables with_vars[q] = [(kind, handle), ...] that observe it (none when
+        with_vars is None); returns ([matrix per request, ordered point (3), variables ...], damping used).
+        An engine whose library has no such entry (the oracle, which solves over the full order) answers
+        through compute_covariances with the blocks [(0, p), *with_vars[q]]."""
+        points = [int(p) for p in points]
+        extra = [[] for _ in points] if with_vars is None else [[(int(k), int(hh)) for k, hh in v] for v in with_vars]
+        if len(extra) != len(points):
+            raise ValueError("with_vars must list the extra variables of every point")
+        if not hasattr(self.lib, self.prefix + "compute_point_covariances"):
+            return self.compute_covariances([[(0, p), *v] for p, v in zip(points, extra)], damping)
+        sizes = [3 + sum(self.var_tangent_dim(k, hh) for k, hh in v) for v in extra]
+        pts = np.array(points, np.int32)
+        st = np.array([0] + list(np.cumsum([len(v) for v in extra])), np.int64)
+        k = np.array([a for v in extra for a, _ in v], np.int32)
+        hh = np.array([b for v in extra for _, b in v], np.int32)
+        out = np.zeros(sum(s * s for s in sizes))
+        used = C.c_double()
+        f = self._fn("compute_point_covariances", [C.c_double, C.c_int64, P, P, P, P, P, C.POINTER(C.c_double)])
+        self._check(f(self.h, float(damping), len(points), pts.ctypes.data, None if with_vars is None else st.ctypes.data,
+                      k.ctypes.data, hh.ctypes.data, out.ctypes.data, C.byref(used)))
+        if all(s == 3 for s in sizes):  # marginals only: one reshape (a map of 300k points is one call)
+            return list(out.reshape(-1, 3, 3).transpose(0, 2, 1).copy()), used.value
+        covs, o = [], 0
+        for s in sizes:
+            covs.append(out[o:o + s * s].reshape(s, s, order="F").copy())
+            o += s * s
+        return covs, used.value
+
+    def point_covariance_times(self):
+        """host time [ms] of the last compute_point_covariances: (prologue, selected inversion, the part
+        after it: requests, kernel, read-back)"""
+        ms = (C.c_double * 3)()
+        self._check(self._fn("point_covariance_times", [C.c_double * 3])(self.h, ms))
+        return tuple(ms)
+
     def var_tangent_dim(self, kind: int, handle: int) -> int:
         """tangent size of one variable (the kind's box-plus dimension; camera records and the IMU
         calibration options decide theirs)"""
