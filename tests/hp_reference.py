@@ -22,8 +22,11 @@ cost = rho(s) / 2 per factor, gradient = rho'(s) J^T e, Hessian = rho'(s) J^T J,
 damped d <- d (1 + lambda) + lambda (addDamping, Optimizer.cpp:136-146; landmark blocks included) and
 step = -(damped H)^-1 gradient.
 
-OUT OF SCOPE: rolling-shutter observations (they need the RollingShutterData tables), inertial factors
-(preintegration) and the priors / random walks.  Nothing here restates them.
+OUT OF SCOPE: rolling-shutter observations.  Their time columns are, by the reference's own definition,
+one-sided numeric differences with eps = 1e-6 (VisualFactor.cpp:131-210), and they need the
+RollingShutterData tables: mp.diff is not the yardstick for a Jacobian that is numeric by specification.
+The inertial, omega-prior, random-walk and prior factors are restated in tests/hp_small_factors.py, which
+builds on this module's SE3, camera record and loss.
 """
 from __future__ import annotations
 
