@@ -43,7 +43,7 @@ pytestmark = pytest.mark.gpu
 K_LM_SMALL_COLS, K_LM_BIG_COLS, K_GRP_IDX = 256, 2048, 1024  # csrc/engine.hpp, csrc/schur.hip
 
 
-# ------------------------------------------------------------------ counting, as finalize.hip does
+# ------------------------------------------------------------------ counting, as symbolic.hip does
 def _free_handles(p, col, kind):
     """observation rows' handle of argument `col`, -1 where absent or constant"""
     h = p.fvars[0][:, col].astype(np.int64).copy()
@@ -57,7 +57,7 @@ _SLOTS = ((1, 1), (2, 5), (3, 4), (4, 2))  # (factor argument, variable kind): p
 
 def panel_columns(p):
     """Y panel columns per landmark: the tangent dimensions of its distinct non-constant pose, extrinsics,
-    intrinsics and velocity blocks (the landmark lists by panel width of finalize.hip)"""
+    intrinsics and velocity blocks (the landmark lists by panel width of symbolic.hip)"""
     cam = p.vars[4]
     tdim = {1: np.full(len(p.vars[1]), 6), 5: np.full(len(p.vars[5]), 6), 2: np.full(len(p.vars[2]), 3),
             4: (cam[:, 1] + (cam[:, 7] != 0) + (cam[:, 8] != 0)).astype(np.int64)}
@@ -77,7 +77,7 @@ def track_lengths(p):
 
 def group_of_rows(p):
     """observation group of every row: the rows sharing their (pose, extrinsics, intrinsics, velocity)
-    blocks, constants counted as absent (finalize.hip's group key); returns (group id per row, sizes)"""
+    blocks, constants counted as absent (symbolic.hip's group key); returns (group id per row, sizes)"""
     key = np.column_stack([_free_handles(p, col, kind) for col, kind in _SLOTS])
     _, inv, counts = np.unique(key, axis=0, return_inverse=True, return_counts=True)
     return inv.ravel(), counts

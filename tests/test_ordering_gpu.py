@@ -1,4 +1,4 @@
-"""The reduced system's nested-dissection order (api.hip finalize): the cut at the thinnest
+"""The reduced system's nested-dissection order (symbolic.hip dissect): the cut at the thinnest
 separator within +-5% of the median (default) against the plain median cut with left separators
 (VIBA_ND_CUTWIN=0).  Both are valid Cholesky orders: the LM step is the same to
 round-off; the thin cut needs fewer tile contributions.  The variables are read at vb_finalize."""

@@ -1,4 +1,4 @@
-"""The two-column supernode factorization (VIBA_SUPERNODE=1 at handle creation; api.hip SnSched,
+"""The two-column supernode factorization (VIBA_SUPERNODE=1 at handle creation; symbolic.hip / host.hpp SnSched,
 solver.hip snpotrf_kernel / sntrsm_kernel) against the oracle and against the column schedule.
 
 A pair (J, J + 1) -- J + 1 the parent of J, J's other rows all rows of J + 1 -- is factored as one

@@ -1,7 +1,8 @@
 // Host side of the HIP LM engine, shared by its translation units: the kernel launchers (factors.hip /
 // solver.hip / ...), host helpers, the schedules and the handle (vb_handle_s).  api.hip: the numeric
-// phases and the LM controller; finalize.hip: vb_finalize (ordering, symbolic analysis, Schur work lists,
-// factorization schedules); covariances.hip; multi.hip: the multi-process building blocks; tools.hip.
+// phases and the LM controller; symbolic.hip: vb_finalize's host-only analysis (ordering, tile pattern,
+// Schur work lists, factorization schedules; symbolic.hpp); finalize.hip: its upload into the handle;
+// covariances.hip; multi.hip: the multi-process building blocks; tools.hip.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -20,6 +21,7 @@
 
 #include "../../include/viba_hip.h"
 #include "engine.hpp"
+#include "symbolic.hpp"
 
 namespace viba {
 // kernels (factors.hip / solver.hip)
@@ -108,16 +110,7 @@ using namespace viba;
 namespace viba_host {
 
 inline thread_local std::string g_err = "";
-constexpr int TS = 64;
-constexpr int kVarData[9] = {3, 7, 3, 3, 24, 7, 32, 7, 4};
 constexpr int kMaxTan[9] = {3, 6, 3, 3, 17, 6, 23, 6, 2};
-constexpr int kNumVars[14] = {5, 6, 9, 10, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1};
-constexpr int kNumConsts[14] = {6, 331, 331, 331, 4, 23, 17, 6, 6, 43, 55, 41, 13, 13};
-// ImuNoiseModelParameters::reset sample variances (imu_types/ImuNoiseModelParameters.h:78-80): accel 3, gyro 3
-constexpr double kDefaultImuNoise[6] = {6.6297049e-3, 6.6297049e-3, 6.6297049e-3, 2.7415568e-05, 2.7415568e-05, 2.7415568e-05};
-const int kFK[14][10] = {{0, 1, 5, 4, 2}, {6, 1, 2, 1, 2, 8}, {6, 1, 2, 3, 1, 2, 3, 7, 8},
-                         {6, 1, 2, 3, 7, 1, 2, 3, 7, 8}, {3, 7}, {6, 6}, {4, 4}, {7, 7}, {5, 5}, {1}, {6}, {4},
-                         {5}, {7}};
 
 inline int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -129,105 +122,10 @@ inline int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess) return fail(VB_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-inline ImuIdx makeJac(int mask) {
-  ImuIdx J;
-  int i = 0;
-  J.gB = (mask & 1) ? (i += 3) - 3 : -1;
-  J.aB = (mask & 2) ? (i += 3) - 3 : -1;
-  J.gS = (mask & 4) ? (i += 3) - 3 : -1;
-  J.aS = (mask & 8) ? (i += 3) - 3 : -1;
-  J.gN = (mask & 16) ? (i += 6) - 6 : -1;
-  J.aN = (mask & 32) ? (i += 3) - 3 : -1;
-  J.rT = (mask & 64) ? (i += 1) - 1 : -1;
-  J.gaT = (mask & 128) ? (i += 1) - 1 : -1;
-  J.size = i;
-  return J;
-}
 inline LossParams makeLoss(double a, double k) {
   LossParams L;
   L.a = a, L.b = a * a, L.k2 = k * k, L.h = 2.0 * a * k - a * a;
   return L;
-}
-
-// symmetric square root U (P = U^T U) of a PSD m x m matrix via cyclic Jacobi eigen-decomposition
-inline void psdSqrt(const double* Pm, int m, double* U) {
-  std::vector<double> A(Pm, Pm + m * m), V(m * m, 0.0);
-  for (int i = 0; i < m; i++) V[i * m + i] = 1.0;
-  for (int sweep = 0; sweep < 60; sweep++) {
-    double off = 0;
-    for (int p = 0; p < m; p++)
-      for (int q = p + 1; q < m; q++) off += A[p * m + q] * A[p * m + q];
-    if (off < 1e-30) break;
-    for (int p = 0; p < m; p++)
-      for (int q = p + 1; q < m; q++) {
-        const double apq = A[p * m + q];
-        if (std::abs(apq) < 1e-300) continue;
-        const double th = 0.5 * (A[q * m + q] - A[p * m + p]) / apq;
-        const double t = (th >= 0 ? 1.0 : -1.0) / (std::abs(th) + std::sqrt(th * th + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < m; k++) {
-          const double akp = A[k * m + p], akq = A[k * m + q];
-          A[k * m + p] = c * akp - s * akq, A[k * m + q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < m; k++) {
-          const double apk = A[p * m + k], aqk = A[q * m + k];
-          A[p * m + k] = c * apk - s * aqk, A[q * m + k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < m; k++) {
-          const double vkp = V[k * m + p], vkq = V[k * m + q];
-          V[k * m + p] = c * vkp - s * vkq, V[k * m + q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  // U = diag(sqrt(lambda)) V^T  (rows = eigenvectors scaled)
-  for (int i = 0; i < m; i++) {
-    const double l = std::sqrt(std::max(0.0, A[i * m + i]));
-    for (int j = 0; j < m; j++) U[i * m + j] = l * V[j * m + i];
-  }
-}
-// upper Cholesky U of P = inverse(cov) (cov SPD, col-major m x m): P = U^T U
-inline bool precisionChol(const double* cov, int m, double* U) {
-  std::vector<double> A(cov, cov + m * m), Pi(m * m, 0.0);
-  // invert via Gauss-Jordan with partial pivoting
-  std::vector<double> I(m * m, 0.0);
-  for (int i = 0; i < m; i++) I[i * m + i] = 1.0;
-  std::vector<double> M(m * m);
-  for (int i = 0; i < m; i++)
-    for (int j = 0; j < m; j++) M[i * m + j] = A[j * m + i];  // row-major
-  for (int c = 0; c < m; c++) {
-    int piv = c;
-    for (int r = c + 1; r < m; r++)
-      if (std::abs(M[r * m + c]) > std::abs(M[piv * m + c])) piv = r;
-    if (std::abs(M[piv * m + c]) < 1e-300) return false;
-    for (int k = 0; k < m; k++) std::swap(M[c * m + k], M[piv * m + k]), std::swap(I[c * m + k], I[piv * m + k]);
-    const double inv = 1.0 / M[c * m + c];
-    for (int k = 0; k < m; k++) M[c * m + k] *= inv, I[c * m + k] *= inv;
-    for (int r = 0; r < m; r++) {
-      if (r == c) continue;
-      const double f = M[r * m + c];
-      if (f == 0.0) continue;
-      for (int k = 0; k < m; k++) M[r * m + k] -= f * M[c * m + k], I[r * m + k] -= f * I[c * m + k];
-    }
-  }
-  // symmetrize P and Cholesky (lower L, row-major), U = L^T
-  std::vector<double> L(m * m, 0.0);
-  for (int i = 0; i < m; i++)
-    for (int j = 0; j < m; j++) Pi[i * m + j] = 0.5 * (I[i * m + j] + I[j * m + i]);
-  for (int j = 0; j < m; j++) {
-    double dd = Pi[j * m + j];
-    for (int k = 0; k < j; k++) dd -= L[j * m + k] * L[j * m + k];
-    if (!(dd > 0)) return false;
-    dd = std::sqrt(dd);
-    L[j * m + j] = dd;
-    for (int i = j + 1; i < m; i++) {
-      double s = Pi[i * m + j];
-      for (int k = 0; k < j; k++) s -= L[i * m + k] * L[j * m + k];
-      L[i * m + j] = s / dd;
-    }
-  }
-  for (int i = 0; i < m; i++)
-    for (int j = 0; j < m; j++) U[i * m + j] = L[j * m + i];
-  return true;
 }
 
 template <typename T>
@@ -256,21 +154,12 @@ using namespace viba_host;
 // One tile-Cholesky schedule (factorSeq): per elimination level the potrf / trsm / fan-in work
 // lists (offsets lvP / lvT / lvU), the fan-in contribution pairs it indexes, and the fan-out solve
 // task lists over the same columns (solver.hip fwd/bwd_fanout_kernel).
-struct Sched {
-  std::vector<int64_t> lvP, lvT, lvU;
-  // levels factored by one potrf + trsm launch (potrf_trsm_kernel): per level the range of its items
-  // (diagonal tile, column, target, row, writer) in ptfD; the diagonal tiles to copy back from Lscr
-  std::vector<int64_t> lvPF;
+struct Sched : SchedShape {
   int32_t *ptfD = nullptr, *ptfDiagD = nullptr;
-  int64_t nPtfDiag = 0;
-  int32_t nLevels = 0;
-  int64_t nPairs = 0;
   int32_t *potrfTileD = nullptr, *potrfColD = nullptr, *trsmDiagD = nullptr, *trsmTargetD = nullptr,
           *trsmColD = nullptr, *updD = nullptr, *fanPairsD = nullptr, *trsmRowD = nullptr;
   int32_t *tasksFD = nullptr, *tasksBD = nullptr, *expFD = nullptr, *expBD = nullptr, *preReadyD = nullptr;
-  int64_t nF = 0, nB = 0, nPreReady = 0;  // preReady: rows whose x is known before the backward solve
   hipGraphExec_t graph[2] = {nullptr, nullptr};  // per tile store (vb_handle_s::tileSet)
-  bool built = false;
 };
 
 // Two-column supernodes (VIBA_SUPERNODE, single handle): where column J + 1 is J's parent in the
@@ -279,15 +168,7 @@ struct Sched {
 // (sntrsm_kernel: L_I1 = A_I1 L11^-T, A_I2 -= L_I1 L21^T, L_I2 = A_I2 L22^-T), so the pair is ONE level
 // of the schedule: about half the levels (launches, dependency gaps, potrf latency chains) of the
 // column schedule.  The fan-in lists leave out the pair-internal contributions (J -> J + 1).
-struct SnSched {
-  int32_t nLevels = 0;
-  int64_t nPairs = 0;                  // fan-in contributions (external to the supernodes)
-  int64_t nSuper = 0, nTwo = 0;        // supernodes, of which two-column
-  std::vector<int64_t> lvU, lvS, lvR;  // per segment: fan-in chunk, supernode and row-item ranges
-  // segments: one level of one stream (nGroups > 1: independent subtrees and the separators above them),
-  // level-major; segL its level, segDep the bit mask of other streams it waits for
-  std::vector<int32_t> segG, segL, segDep;
-  int nGroups = 1;
+struct SnSched : SnSchedShape {
   int32_t *updD = nullptr, *fanPairsD = nullptr;
   int32_t *potD = nullptr;  // per supernode: tile (J, J), J, tile (J + 1, J) or -1, tile (J + 1, J + 1) or -1
   int32_t *rowD = nullptr;  // per row item: tile (I, J) or -1, tile (I, J + 1) or -1, J, J + 1 or -1, I,
@@ -295,16 +176,12 @@ struct SnSched {
   // levels with few rows: diagonal block + one row per block in one launch (snpotrf_trsm8_kernel); items
   // (tile (J, J), J, tile (J + 1, J) or -1, tile (J + 1, J + 1) or -1, tile (I, J) or -1, tile (I, J + 1) or
   // -1, I or -1, writer); their factored diagonal-block tiles come back from the scratch at the end
-  std::vector<int64_t> lvF;
   int32_t *fusD = nullptr, *copyD = nullptr;
-  int64_t nCopy = 0;
   // the solves' diagonal-tile inverses: of the columns factored in place before the top separators' chain
   // (invEarlyD, queued on a free stream when the chain starts) and of the rest (invLateD, after the join)
   int32_t *invEarlyD = nullptr, *invLateD = nullptr;
-  int64_t nInvEarly = 0, nInvLate = 0;
 
   hipGraphExec_t graph[2] = {nullptr, nullptr};
-  bool built = false;
 };
 
 struct vb_handle_s {
@@ -338,7 +215,6 @@ struct vb_handle_s {
   double *refBackD = nullptr, *refAccD = nullptr;
   bool finalized = false;
   Dev d;
-  std::vector<void*> allocs;
   // symbolic (host)
   std::vector<int32_t> rvKind, rvHandle, rvDim;
   std::vector<int64_t> rvOff;

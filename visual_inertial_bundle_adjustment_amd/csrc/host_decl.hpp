@@ -1,5 +1,5 @@
 // Declarations of the host functions the engine's translation units share (host.hpp): api.hip defines
-// all but doFinalize / buildSupernodes (finalize.hip).
+// all but doFinalize (finalize.hip).
 #pragma once
 
 namespace viba_host {
