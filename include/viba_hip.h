@@ -509,6 +509,53 @@ int vb_spec_commit(vb_handle h, int use);
  * controller's phase clock attributes them to that iteration, as vb_optimize's vb_phase_times does */
 int vb_spec_phase_ms(vb_handle h, double* out2);
 
+/* ---------------------------------------------------------------- residual report
+ * What ark_vi_ba prints before and after the solve (SingleSessionProblem::showHistogram,
+ * SingleSessionProblem.cpp:512-521 -> Histograms::show, viba/problem/Histograms.cpp:46-137; called at
+ * interfaces/ark/main_AriaKit_ViBa.cpp:72,113) and the rawError / unweightedError logs of the add* methods,
+ * evaluated on the device from the factors the handle holds.  Per factor i of a kind, in vb_add_factors
+ * order (lib/small_thing/Factor.h:172-232):
+ *   raw            rawError(i): the functor's return; vb_factor_error_size doubles per row -- visual 2 |
+ *                  inertial kinds 9, 9, 9 | omega prior 3 | random walks 23, 17, 6, 6 | priors 6, 23, 17, 6, 6;
+ *                  the calibration kinds' enabled entries first, the padded rows zero-filled
+ *   sq_unweighted  unweightedSquaredError(i) = 0.5 |e|^2
+ *   sq_weighted    covWeightedSquaredError(i) = 0.5 e^T P e; P exists for the inertial kinds (inverse rvpCov)
+ *                  and the pose prior (H), every other functor whitens its own return: equal to sq_unweighted
+ *   cost           singleCost(i) = computeSingleCost(i, false) = 0.5 rho(e^T P e): not "comparable", the
+ *                  stored cache is neither read nor written
+ *   valid          0 for a failing factor (visual kinds only), whose other outputs are 0
+ * Both calls evaluate at the current variables with the rolling-shutter tables as they currently are (the
+ * rule of vb_refine_points: the reference's report reads the tables of the last preStepCallback), and change
+ * nothing of the handle's LM state: not the cost cache, the scalar / error-word slots of an iteration in
+ * flight, the step or the spare speculative buffers.  VB_E_STATE before vb_finalize; VB_E_UNSUPPORTED on a
+ * landmark shard or a partitioned rank; VB_E_RANGE for an out-of-range rolling-shutter lookup
+ * (RollingShutterData.cpp:82-91); VB_E_ARG for a bad kind, rows outside the kind's factors, a bad `which`,
+ * `which` 2-4 on a non-inertial kind, edges not strictly increasing, a group id outside [0, n_groups),
+ * n_groups above VB_REPORT_MAX_GROUPS or n_edges above VB_REPORT_MAX_EDGES (one workgroup's bin table of
+ * 64 x 33 32-bit counts stays in 8448 B of LDS; enough for per-camera grouping). */
+int vb_factor_error_size(int kind);
+/* rows [first, first + n) of `kind`; any output may be NULL */
+int vb_factor_errors(vb_handle h, int kind, int64_t first, int64_t n, double* raw, double* sq_unweighted,
+                     double* sq_weighted, double* cost, uint8_t* valid);
+#define VB_ERR_UNWEIGHTED 0 /* sqrt(2 * unweightedSquaredError)  = |e|         (Histograms.cpp:214) */
+#define VB_ERR_WEIGHTED 1   /* sqrt(2 * covWeightedSquaredError) = sqrt(e'Pe)  (Histograms.cpp:161,217,388,505) */
+#define VB_ERR_ROT_DEG 2    /* inertial kinds only: |e[0:3]| in degrees        (Histograms.cpp:376) */
+#define VB_ERR_VEL_CM_S 3   /*                      |e[3:6]| * 100             (Histograms.cpp:377) */
+#define VB_ERR_POS_CM 4     /*                      |e[6:9]| * 100             (Histograms.cpp:378) */
+#define VB_REPORT_MAX_GROUPS 64
+#define VB_REPORT_MAX_EDGES 32
+/* Histogram of one error of every factor of `kind` per group (viba/common/Histogram.cpp:18-56: n_edges
+ * edges make n_edges + 1 bins and a value goes to bin #(edges <= value), as std::upper_bound -- a value on an
+ * edge into the upper bin, one below the first edge into bin 0).  group_of_factor: host, one id per factor in
+ * vb_add_factors order, NULL = one group.  A failing factor counts in n_factors and n_failing, is not binned
+ * and adds no cost (Histograms.cpp:206-212).  Outputs (each may be NULL): counts n_groups x (n_edges + 1),
+ * row-major, exact; cost n_groups, the sum of singleCost; n_factors, n_failing n_groups each. */
+int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const int32_t* group_of_factor,
+                       int32_t n_edges, const double* edges, int64_t* counts, double* cost, int64_t* n_factors,
+                       int64_t* n_failing);
+/* device time [ms] of the last vb_error_histogram's kernels (measurement aid) */
+int vb_report_device_ms(vb_handle h, double* ms);
+
 /* the HIP stream of the handle (hipStream_t), for interop with torch / RCCL */
 void* vb_stream(vb_handle h);
 

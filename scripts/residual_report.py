@@ -1,0 +1,60 @@
+"""The residual report (report.residual_report: vb_error_histogram / vb_factor_errors) of a synthetic config:
+prints it, and times it -- the wall time of the full report, the device time of the visual histogram pass
+(visual_report_kernel, csrc/factors.hip) and, beside it, vb_bench_kernel(15): the visual cost pass of the
+same build, which does the same evaluation without the binning.
+
+    python scripts/residual_report.py [config] [--simple] [--precision fp64|mixed]      (default C)
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from visual_inertial_bundle_adjustment_amd import kinds as K  # noqa: E402
+from visual_inertial_bundle_adjustment_amd import report as R  # noqa: E402
+from visual_inertial_bundle_adjustment_amd import synth  # noqa: E402
+from visual_inertial_bundle_adjustment_amd.engine import HipEngine  # noqa: E402
+
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+which = args[0] if args else "C"
+simple = "--simple" in sys.argv
+precision = sys.argv[sys.argv.index("--precision") + 1] if "--precision" in sys.argv else "fp64"
+p = synth.generate(synth.config(which))
+g = HipEngine(imu_calib_options=p.imu_calib_options, precision=precision)
+synth.load_into(g, p)
+print(f"config {which} ({precision}): {p.summary()}", flush=True)
+rep = R.residual_report(g, simple_stats=simple)  # the first call pays the kernels' load and the report's setup
+print(rep.format())
+cost, _ = g.cost(False)
+rest = sum(float(g.factor_errors(k)["cost"].sum()) for k in (K.F_POSE_PRIOR,) if g.num_factors(k))
+print(f"sum of the cost contributions {rep.total_cost() + rest:.12e} (pose priors, which the report leaves out: {rest:.3e}); "
+      f"cost pass {cost:.12e}")
+
+wall = []
+for _ in range(5):
+    g.synchronize()
+    t = time.perf_counter()
+    R.residual_report(g, simple_stats=simple)
+    wall.append(1e3 * (time.perf_counter() - t))
+edges = R.weighted_histogram().edges
+cams = p.fvars[0][:, 3].astype(np.int32)
+n_groups = int(cams.max()) + 1
+one, grouped, call = [], [], []
+for _ in range(5):
+    t = time.perf_counter()
+    g.error_histogram(K.F_VISUAL, K.ERR_WEIGHTED, edges)
+    call.append(1e3 * (time.perf_counter() - t))
+    one.append(g.report_device_ms())
+    if n_groups <= K.REPORT_MAX_GROUPS:
+        g.error_histogram(K.F_VISUAL, K.ERR_WEIGHTED, edges, cams, n_groups)
+        grouped.append(g.report_device_ms())
+cost_us = g.bench_kernel(15, 50)
+print(f"full report: {np.median(wall):.2f} ms wall (median of 5; {min(wall):.2f} to {max(wall):.2f})")
+print(f"visual histogram pass ({len(cams)} factors): {1e3 * np.median(one):.1f} us on the device, one group"
+      + (f"; {1e3 * np.median(grouped):.1f} us with {n_groups} groups by camera record" if grouped else "")
+      + f"; {np.median(call):.2f} ms wall per vb_error_histogram call")
+print(f"visual cost pass, vb_bench_kernel(15): {cost_us:.1f} us; histogram pass / cost pass = "
+      f"{1e3 * np.median(one) / cost_us:.2f}")
+g.close()

@@ -640,12 +640,15 @@ def save_outputs(out_dir: str, engine, p: SessionProblem, sd: SessionData):
 
 
 def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, settings: InitSettings | None = None,
-                optimizer_settings=None, refine: bool = True, log=print):
+                optimizer_settings=None, refine: bool = True, log=print, show_histogram: bool = False,
+                simple_stats: bool = False):
     """ark_vi_ba (interfaces/ark/main_AriaKit_ViBa.cpp:32-133) on a session folder: load, build indices,
     build the problem, rolling-shutter tables, refinePoints, Optimizer::optimize (with the per-iteration
     rolling-shutter rebuild and, under settings.recompute_preint, the preintegration recompute of the
     preStepCallback), then the three output files.  engine_factory(problem) -> engine (default: the HIP
-    engine).  Returns (engine, problem, summary)."""
+    engine).  show_histogram: log the residual report (report.residual_report: problem.showHistogram,
+    main_AriaKit_ViBa.cpp:72,113) after refinePoints and after optimize, when the engine has the report
+    calls.  Returns (engine, problem, summary)."""
     from .engine import HipEngine, Settings
     s = settings or InitSettings()
     sd = SessionData.load(in_dir, load_imu=True)
@@ -661,9 +664,17 @@ def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, se
         (c0, c1), _ = e.refine_points()
         if log:
             log(f"[ark] refinePoints: visual cost {c0:.6g} -> {c1:.6g}")
+
+    def histogram():
+        if show_histogram and log and hasattr(e, "error_histogram") and hasattr(e, "factor_errors"):
+            from .report import residual_report
+            log(residual_report(e, simple_stats=simple_stats).format())
+
+    histogram()
     summary = e.optimize(optimizer_settings or Settings.default())
     if log:
         log(f"[ark] optimize: {summary.initial_cost:.6g} -> {summary.final_cost:.6g} in {summary.num_iterations} iterations")
+    histogram()
     if out_dir:
         save_outputs(out_dir, e, p, sd)
     return e, p, summary

@@ -614,6 +614,7 @@ int vb_destroy(vb_handle h) {
   if (!h) return 0;
   hipSetDevice(h->cfg.device);
   hipStreamSynchronize(h->st);
+  reportFree(h);
   Dev& d = h->d;
   void* ptrs[] = {d.rvKind, d.rvHandle, d.rvDim, d.rvOff, d.rvRowEnd, d.obCostOrder, d.obPack, d.obCP, d.obPose, d.obExtr, d.obIntr, d.obVel,
                   d.obRS, d.obPt, d.obRed, d.obCol, d.obC, d.cache, d.Jt, d.lmObs, d.lmY, d.lmBlk, d.blkRed,

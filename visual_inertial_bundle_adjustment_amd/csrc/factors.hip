@@ -12,6 +12,7 @@
 //                         factor, scattered into the reduced tiles / gradient with fp64 atomics.
 #include "device_math.hpp"
 #include "engine.hpp"
+#include "report.hpp"
 #include <algorithm>
 
 namespace viba {
@@ -383,6 +384,58 @@ __global__ void __launch_bounds__(256) visual_cost_kernel(Dev d, int comparable,
   block_sum_atomic<4>(acc, d.redS + (blockIdx.x & 63) * 8 + 1);
 }
 
+// Residual report of the visual factors (Histograms::showHistogramsVisual, Histograms.cpp:185-255, and the
+// rawError / unweightedError logs): the cost pass's evaluation at the current variables and tables, not
+// comparable, reading neither the ResultCache nor the reduction / error slots of the LM loop (err is the
+// report's own word).  The functor whitens its return by sqrtH, so unweightedSquaredError =
+// covWeightedSquaredError = 0.5 |e|^2 and singleCost = 0.5 rho(|e|^2) (Factor.h:172-232).
+//   Hist:  item t = position t of obCostOrder (global shutter first: a wave takes one evaluation path);
+//          every workgroup walks its share of the positions and bins sqrt(2 * 0.5 |e|^2) into an LDS
+//          table [group][bin], flushed once at the end (rep_flush): no per-observation buffer
+//   !Hist: item t = row R.first + t of vb_add_factors order (posOfRow: its position), the requested
+//          arrays stored at t, coalesced
+template <bool Hist>
+__global__ void __launch_bounds__(256) visual_report_kernel(Dev d, const int32_t* posOfRow, RepRows R, RepHist H,
+                                                            int32_t* err) {
+  __shared__ RepTable tab;
+  if (Hist) rep_clear(tab, H);
+  const int64_t n = Hist ? d.nObs : R.n;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
+    const int64_t i = Hist ? t : posOfRow[R.first + t];
+    const int4 pa = reinterpret_cast<const int4*>(d.obPack)[2 * i], pb = reinterpret_cast<const int4*>(d.obPack)[2 * i + 1];
+    VisOut v;
+    v.Jintr = nullptr;
+    v.e[0] = v.e[1] = 0.0;
+    bool oor = false, ok;
+    const double* obsC = d.obCP + i * 6;
+    const double* Xp = d.var[0] + (int64_t)pa.y * 3;
+    v3 X = mk(Xp[0], Xp[1], Xp[2]);
+    se3 Tbw = se3_load(d.var[1] + (int64_t)pa.z * 7);
+    se3 Tcb = se3_load(d.var[5] + (int64_t)pa.w * 7);
+    const double* cam = d.var[4] + (int64_t)pb.x * 24;
+    const int rs = pb.y;
+    if (rs < 0) {
+      ok = vis_eval<false>(obsC, X, Tbw, Tcb, cam, v);
+    } else {
+      const double* vp = d.var[2] + (int64_t)pb.z * 3;
+      ok = rs_eval<false>(d, obsC, rs, X, Tbw, Tcb, cam, mk(vp[0], vp[1], vp[2]), false, false, v, &oor);
+      if (oor) atomicOr(err, 1);
+    }
+    const double s = ok ? v.e[0] * v.e[0] + v.e[1] * v.e[1] : 0.0;
+    const double cost = ok ? 0.5 * huber_val(d.reproj.a, d.reproj.b, d.reproj.k2, d.reproj.h, s) : 0.0;
+    if (Hist) {
+      rep_add(tab, H, H.grp ? H.grp[i] : 0, ok, sqrt(2.0 * (0.5 * s)), cost);
+    } else {
+      if (R.raw) R.raw[2 * t] = ok ? v.e[0] : 0.0, R.raw[2 * t + 1] = ok ? v.e[1] : 0.0;
+      if (R.squ) R.squ[t] = 0.5 * s;
+      if (R.sqw) R.sqw[t] = 0.5 * s;
+      if (R.cost) R.cost[t] = cost;
+      if (R.valid) R.valid[t] = ok ? 1 : 0;
+    }
+  }
+  if (Hist) rep_flush(tab, H);
+}
+
 // ------------------------------------------------------------------ small factors
 constexpr int kMaxM = kSmallRows;
 constexpr int kMaxCols = kSmallCols;
@@ -622,11 +675,16 @@ __constant__ int kFK[14][10] = {
 __constant__ int kNV[14] = {5, 6, 9, 10, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1};
 
 // evaluation of factor k of kind FK (k >= a.n: nothing); returns this lane's cost term
-template <int FK>
-__device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, int64_t k) {
+// Report (the residual report, small_report_kernel): evaluate only -- the residual as the functor returns
+// it (rawError, Factor.h:172-232; the calibration kinds' enabled entries compacted, zero-filled), half its
+// squared norm, half the squared whitened norm and singleCost go to row k - rep->first of rep; no staging,
+// meta or Jacobian is written (a.mode is 2 there).  The other instantiation is untouched by it.
+template <int FK, bool Report = false>
+__device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, int64_t k, const RepRows* rep = nullptr) {
   double acc[1] = {0.0};
   constexpr int mRows = (FK >= 1 && FK <= 3) ? 9 : FK == 4 ? 3 : (FK == 5 || FK == 10) ? 23 : (FK == 6 || FK == 11) ? 17 : 6;
-  if (a.mode != 2) {
+  constexpr bool kCompact = FK == 5 || FK == 10 || FK == 6 || FK == 11;  // Report: raw rows written in the kind's loop
+  if (!Report && a.mode != 2) {
     // the wave's 64 staging slots (consecutive factors) zeroed over their first mRows rows with the
     // lanes on consecutive 16 B: one factor's rows zeroed per lane made every store instruction 64
     // scattered 8-byte writes
@@ -643,7 +701,7 @@ __device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, i
   if (k < a.n) {
     SmallEval E;
     const int64_t slot = d.sf[FK].stage + k;
-    E.J = (double(*)[kMaxCols])(d.sJ + slot * kSmallJ);
+    E.J = Report ? nullptr : (double(*)[kMaxCols])(d.sJ + slot * kSmallJ);
     constexpr int nv = (FK == 0) ? 5 : (FK == 1) ? 6 : (FK == 2) ? 9 : (FK == 3) ? 10 : (FK <= 8) ? 2 : 1;  // kNV
     const int32_t* vi = a.vars + k * nv;
     const double* c = a.consts + k * a.nc;
@@ -718,11 +776,14 @@ __device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, i
         se3 Tib = se3_load(d.var[7] + (int64_t)vi[1] * 7);
         r = scl(1.0 / sig, sub(om, qrot(qinv(Tib.R), wI)));
         // -R^T * (-hat(-w)) / sig = -R^T hat(w) / sig
-        m3 B = mmul(mT(qmat(Tib.R)), hat(wI));
-        for (int i = 0; i < 3; i++)
-          for (int j = 0; j < 3; j++) E.J[i][E.col[1] + j] = 0.0, E.J[i][E.col[1] + 3 + j] = -B.a[i][j] / sig;
+        if constexpr (!Report) {
+          m3 B = mmul(mT(qmat(Tib.R)), hat(wI));
+          for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) E.J[i][E.col[1] + j] = 0.0, E.J[i][E.col[1] + 3 + j] = -B.a[i][j] / sig;
+        }
       }
-      for (int i = 0; i < 3; i++) E.J[i][E.col[0] + i] = 1.0 / sig;
+      if constexpr (!Report)
+        for (int i = 0; i < 3; i++) E.J[i][E.col[0] + i] = 1.0 / sig;
       E.e[0] = r.x, E.e[1] = r.y, E.e[2] = r.z;
     } else if (FK == 5 || FK == 10) {  // imu calib RW / prior (residual padded to 23)
       // rows in the canonical error-state order (a disabled block leaves zero rows: J^T J and J^T e
@@ -751,15 +812,22 @@ __device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, i
         else dv = (v[30] - v[31]) - (r[30] - r[31]);
         if (FK == 5) {
           E.e[q] = dv * c[j];
-          E.J[q][E.col[0] + j] = -c[j];
-          E.J[q][E.col[1] + j] = c[j];
+          if constexpr (!Report) {
+            E.J[q][E.col[0] + j] = -c[j];
+            E.J[q][E.col[1] + j] = c[j];
+          }
         } else {
           const double sq = sqrt(c[32 + j]);
           E.e[q] = dv * sq;
-          E.J[q][E.col[0] + j] = sq;
+          if constexpr (!Report) E.J[q][E.col[0] + j] = sq;
         }
+        if constexpr (Report)
+          if (rep->raw) rep->raw[(k - rep->first) * mRows + j] = E.e[q];
         j++;
       }
+      if constexpr (Report)
+        if (rep->raw)
+          for (; j < mRows; j++) rep->raw[(k - rep->first) * mRows + j] = 0.0;
     } else if (FK == 6 || FK == 11) {  // cam intrinsics RW / prior (residual padded to 17)
       // rows: projection parameter q (q < np), 15 readout, 16 time offset (as above: static indices)
       E.m = 17;
@@ -775,14 +843,21 @@ __device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, i
         const double dv = q < 15 ? v[9 + q] - b[9 + q] : q == 15 ? v[5] - b[5] : v[6] - b[6];
         const double sq = FK == 6 ? c[j] : sqrt(c[24 + j]);
         E.e[q] = dv * sq;
-        if (FK == 6) {
-          E.J[q][E.col[0] + j] = -sq;
-          E.J[q][E.col[1] + j] = sq;
-        } else {
-          E.J[q][E.col[0] + j] = sq;
+        if constexpr (!Report) {
+          if (FK == 6) {
+            E.J[q][E.col[0] + j] = -sq;
+            E.J[q][E.col[1] + j] = sq;
+          } else {
+            E.J[q][E.col[0] + j] = sq;
+          }
         }
+        if constexpr (Report)
+          if (rep->raw) rep->raw[(k - rep->first) * mRows + j] = E.e[q];
         j++;
       }
+      if constexpr (Report)
+        if (rep->raw)
+          for (; j < mRows; j++) rep->raw[(k - rep->first) * mRows + j] = 0.0;
     } else {  // SE3 RW (7, 8), pose prior (9), SE3 priors (12, 13)
       E.m = 6;
       const int vk = (FK == 7 || FK == 13) ? 7 : (FK == 9 ? 1 : 5);
@@ -797,20 +872,22 @@ __device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, i
       }
       double lg[6], Ji[36];
       se3_log(err, lg);
-      se3_leftJacInv(lg, Ji);
+      if constexpr (!Report) se3_leftJacInv(lg, Ji);
       for (int i = 0; i < 6; i++) E.e[i] = lg[i] * sq[i];
-      const int cn = (FK == 7 || FK == 8) ? E.col[1] : E.col[0];
-      for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) E.J[i][cn + j] = sq[i] * Ji[i * 6 + j];
-      if (FK == 7 || FK == 8) {
-        double A[36];
-        se3_Adj(err, A);
+      if constexpr (!Report) {
+        const int cn = (FK == 7 || FK == 8) ? E.col[1] : E.col[0];
         for (int i = 0; i < 6; i++)
-          for (int j = 0; j < 6; j++) {
-            double x = 0;
-            for (int q = 0; q < 6; q++) x += Ji[i * 6 + q] * A[q * 6 + j];
-            E.J[i][E.col[0] + j] = -sq[i] * x;
-          }
+          for (int j = 0; j < 6; j++) E.J[i][cn + j] = sq[i] * Ji[i * 6 + j];
+        if (FK == 7 || FK == 8) {
+          double A[36];
+          se3_Adj(err, A);
+          for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++) {
+              double x = 0;
+              for (int q = 0; q < 6; q++) x += Ji[i * 6 + q] * A[q * 6 + j];
+              E.J[i][E.col[0] + j] = -sq[i] * x;
+            }
+        }
       }
       if (FK == 9) {
         whiten = true;
@@ -821,6 +898,16 @@ __device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, i
     // the Jacobian is whitened by small_assemble_kernel.  m is the kind's residual size (E.m), a
     // compile-time bound so E.e stays in registers
     constexpr int m = mRows;
+    if constexpr (Report) {
+      const int64_t row = k - rep->first;
+      double su = 0;
+#pragma unroll
+      for (int i = 0; i < m; i++) su += E.e[i] * E.e[i];
+      if (rep->squ) rep->squ[row] = 0.5 * su;
+      if (!kCompact && rep->raw)
+#pragma unroll
+        for (int i = 0; i < m; i++) rep->raw[row * m + i] = E.e[i];
+    }
     if (whiten) {
       double te[m];
 #pragma unroll
@@ -839,7 +926,13 @@ __device__ __forceinline__ double small_eval(const Dev& d, const SmallArgs& a, i
     double rho, drho;
     if (useImuLoss) huber_jet2(d.imu.a, d.imu.b, d.imu.k2, d.imu.h, sq, rho, drho);
     else rho = sq, drho = 1.0;
-    if (a.mode == 2) {
+    if constexpr (Report) {
+      // covWeightedSquaredError and singleCost = computeSingleCost(i, false) (Factor.h:172-232)
+      const int64_t row = k - rep->first;
+      acc[0] = 0.5 * (useImuLoss ? huber_val(d.imu.a, d.imu.b, d.imu.k2, d.imu.h, sq) : sq);
+      if (rep->sqw) rep->sqw[row] = 0.5 * sq;
+      if (rep->cost) rep->cost[row] = acc[0];
+    } else if (a.mode == 2) {
       acc[0] = 0.5 * (useImuLoss ? huber_val(d.imu.a, d.imu.b, d.imu.k2, d.imu.h, sq) : sq);
     } else {
       acc[0] = 0.5 * rho;
@@ -894,6 +987,32 @@ __global__ void __launch_bounds__(64) small_kernel(Dev d, SmallLaunch L) {
   }
   if (!L.countCost) acc[0] = 0.0;
   block_sum_atomic<1>(acc, d.red + (L.a[1].mode == 2 ? 1 : 0));
+}
+
+// Residual report of one small kind: rows [R.first, R.first + R.n) through small_eval's evaluate-only
+// instantiation, one lane per factor; adds into no reduction slot
+template <int FK, int LO, int HI>
+__device__ __forceinline__ void small_case_report(const Dev& d, const SmallArgs& a, int fk, int64_t k, const RepRows& R) {
+  if constexpr (FK >= LO && FK <= HI) {
+    if (fk == FK) small_eval<FK, true>(d, a, k, &R);
+  }
+}
+template <int LO, int HI>
+__global__ void __launch_bounds__(64) small_report_kernel(Dev d, SmallArgs a, int fk, RepRows R) {
+  const int64_t k = R.first + (int64_t)blockIdx.x * 64 + threadIdx.x;
+  small_case_report<1, LO, HI>(d, a, fk, k, R);
+  small_case_report<2, LO, HI>(d, a, fk, k, R);
+  small_case_report<3, LO, HI>(d, a, fk, k, R);
+  small_case_report<4, LO, HI>(d, a, fk, k, R);
+  small_case_report<5, LO, HI>(d, a, fk, k, R);
+  small_case_report<6, LO, HI>(d, a, fk, k, R);
+  small_case_report<7, LO, HI>(d, a, fk, k, R);
+  small_case_report<8, LO, HI>(d, a, fk, k, R);
+  small_case_report<9, LO, HI>(d, a, fk, k, R);
+  small_case_report<10, LO, HI>(d, a, fk, k, R);
+  small_case_report<11, LO, HI>(d, a, fk, k, R);
+  small_case_report<12, LO, HI>(d, a, fk, k, R);
+  small_case_report<13, LO, HI>(d, a, fk, k, R);
 }
 
 // Assembly of the staged small factors, one wave per factor (4 per workgroup): whitened Jacobian
@@ -1303,6 +1422,27 @@ void launch_small_eval(const Dev& d, int mode, double* gOut, hipStream_t st) {
   const int32_t nImu = L.first[4] - L.first[1], nRest = L.first[14] - L.first[4];
   if (nImu > 0) hipLaunchKernelGGL((small_kernel<1, 3>), dim3((unsigned)nImu), dim3(64), 0, st, d, L);
   if (nRest > 0) hipLaunchKernelGGL((small_kernel<4, 13>), dim3((unsigned)nRest), dim3(64), 0, st, d, L);
+}
+
+// residual report (report.hpp)
+void launch_visual_rows(const Dev& d, const int32_t* posOfRow, const RepRows& R, int32_t* err, hipStream_t st) {
+  if (R.n <= 0) return;
+  hipLaunchKernelGGL(visual_report_kernel<false>, dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st, d, posOfRow, R,
+                     RepHist{}, err);
+}
+void launch_visual_hist(const Dev& d, const RepHist& H, int32_t* err, int blocks, hipStream_t st) {
+  if (d.nObs <= 0) return;
+  const int64_t nb = std::min<int64_t>((d.nObs + 255) / 256, std::max(1, blocks));
+  hipLaunchKernelGGL(visual_report_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, d, (const int32_t*)nullptr,
+                     RepRows{}, H, err);
+}
+void launch_small_rows(const Dev& d, int fk, const RepRows& R, hipStream_t st) {
+  if (R.n <= 0) return;
+  const SmallFactors& f = d.sf[fk];
+  const SmallArgs a{R.first + R.n, f.vars, f.consts, f.nc, 2, nullptr};
+  const dim3 grid((unsigned)((R.n + 63) / 64));
+  if (fk <= 3) hipLaunchKernelGGL((small_report_kernel<1, 3>), grid, dim3(64), 0, st, d, a, fk, R);
+  else hipLaunchKernelGGL((small_report_kernel<4, 13>), grid, dim3(64), 0, st, d, a, fk, R);
 }
 
 void launch_small_assemble(const Dev& d, int mode, double* gOut, hipStream_t st, int part = 3);

@@ -81,6 +81,8 @@ void copyToHandle(vb_handle h, const Symbolic& A) {
   h->nLevels = A.pat.nLevels;
   h->nPairs = A.sch[0].nPairs + A.sch[1].nPairs;
   h->costRsB[0] = A.cost.rsBegin[0], h->costRsB[1] = A.cost.rsBegin[1];
+  h->visRowOfPos.resize(A.cost.order.size());
+  for (size_t i = 0; i < A.cost.order.size(); i++) h->visRowOfPos[i] = (int32_t)A.obs.perm[A.cost.order[i]];
   if (A.preint.present) h->piNoise = A.preint.noise;
 }
 

@@ -184,6 +184,8 @@ struct SnSched : SnSchedShape {
   hipGraphExec_t graph[2] = {nullptr, nullptr};
 };
 
+struct ReportState;  // report.hip
+
 struct vb_handle_s {
   vb_config cfg;
   hipStream_t st = nullptr;
@@ -213,6 +215,10 @@ struct vb_handle_s {
   int64_t* refStartD = nullptr;
   int32_t *refObsD = nullptr, *refPtD = nullptr;
   double *refBackD = nullptr, *refAccD = nullptr;
+  // residual report (report.hip): the visual factor row (vb_add_factors order) at every position of
+  // obCostOrder, and the report's device state, made at its first call
+  std::vector<int32_t> visRowOfPos;
+  ReportState* rep = nullptr;
   bool finalized = false;
   Dev d;
   // symbolic (host)

@@ -18,6 +18,8 @@ int solveReduced(vb_handle h, int which = 0, int phases = 3);
 void backSubstitute(vb_handle h, int which);
 // vb_finalize (finalize.hip)
 int doFinalize(vb_handle h);
+// the residual report's device state (report.hip)
+void reportFree(vb_handle h);
 }  // namespace viba_host
 
 extern "C" {

@@ -117,6 +117,7 @@ class CEngineBase:
         self.lib = lib
         self.h = handle
         self.nvars = [0] * NUM_VAR_KINDS
+        self.nfactors = {}  # factors added per kind
         self._keep = []
 
     # ---------------------------------------------------------------- plumbing
@@ -154,6 +155,10 @@ class CEngineBase:
                                      C.POINTER(C.c_int32), _dp])
         self._check(f(self.h, kind, n, v.ctypes.data_as(C.POINTER(C.c_int32)),
                       iv.ctypes.data_as(C.POINTER(C.c_int32)), cs.ctypes.data_as(_dp)))
+        self.nfactors[int(kind)] = self.nfactors.get(int(kind), 0) + n
+
+    def num_factors(self, kind: int) -> int:
+        return self.nfactors.get(int(kind), 0)
 
     def set_rs_tables(self, offsets, samples, interp, gravity):
         off = _arr(offsets, np.int64)
@@ -552,6 +557,47 @@ class HipEngine(CEngineBase):
                                           C.POINTER(Summary)])(
             self.h, C.byref(s), lcb, pcb, None, C.byref(out)))
         return out
+
+    # ---------------------------------------------------------------- residual report
+    def factor_errors(self, kind: int, first: int = 0, n: int | None = None) -> dict:
+        """Per-factor errors of rows [first, first + n) of `kind` in add_factors order (vb_factor_errors;
+        Factor.h:172-232): dict of raw (n, FACTOR_ERROR_SIZE[kind]), sq_unweighted, sq_weighted, cost (n)
+        and valid (n, bool; a failing visual factor has valid False and zeros)."""
+        from .kinds import FACTOR_ERROR_SIZE
+        kind, first = int(kind), int(first)
+        if n is None:
+            n = max(0, self.num_factors(kind) - first)
+        n = int(n)
+        m = FACTOR_ERROR_SIZE[kind] if 0 <= kind < len(FACTOR_ERROR_SIZE) else 1
+        raw, valid = np.zeros((max(n, 0), m)), np.zeros(max(n, 0), np.uint8)
+        squ, sqw, cost = (np.zeros(max(n, 0)) for _ in range(3))
+        f = self._fn("factor_errors", [C.c_int, C.c_int64, C.c_int64, P, P, P, P, P])
+        self._check(f(self.h, kind, first, n, raw.ctypes.data, squ.ctypes.data, sqw.ctypes.data, cost.ctypes.data,
+                      valid.ctypes.data))
+        return {"raw": raw, "sq_unweighted": squ, "sq_weighted": sqw, "cost": cost, "valid": valid.astype(bool)}
+
+    def error_histogram(self, kind: int, which: int, edges, groups=None, n_groups: int = 1) -> dict:
+        """Histogram of one error (kinds.ERR_*) of every factor of `kind`, per group (vb_error_histogram;
+        Histogram.cpp:18-56 binning: len(edges) + 1 bins, a value on an edge into the upper bin).  groups:
+        one id in [0, n_groups) per factor in add_factors order, None = one group.  Returns counts
+        (n_groups, len(edges) + 1), cost (n_groups: sum of singleCost), n_factors, n_failing (n_groups)."""
+        e = _arr(edges, np.float64).reshape(-1)
+        g = None if groups is None else _arr(groups, np.int32).reshape(-1)
+        if g is not None and len(g) != self.num_factors(kind):
+            raise ValueError(f"groups must name every factor of kind {kind} ({self.num_factors(kind)}), not {len(g)}")
+        ng = max(int(n_groups), 0)
+        counts = np.zeros((ng, len(e) + 1), np.int64)
+        cost, nf, nx = np.zeros(ng), np.zeros(ng, np.int64), np.zeros(ng, np.int64)
+        f = self._fn("error_histogram", [C.c_int, C.c_int, C.c_int32, P, C.c_int32, P, P, P, P, P])
+        self._check(f(self.h, int(kind), int(which), int(n_groups), None if g is None else g.ctypes.data, len(e),
+                      e.ctypes.data, counts.ctypes.data, cost.ctypes.data, nf.ctypes.data, nx.ctypes.data))
+        return {"counts": counts, "cost": cost, "n_factors": nf, "n_failing": nx}
+
+    def report_device_ms(self) -> float:
+        """device time [ms] of the last error_histogram's kernels (vb_report_device_ms)"""
+        ms = C.c_double()
+        self._check(self._fn("report_device_ms", [_dp])(self.h, C.byref(ms)))
+        return ms.value
 
     def profile_kernel(self, family: int):
         self._check(self._fn("profile_kernel", [C.c_int])(self.h, family))
