@@ -9,6 +9,7 @@ path (initAllParams, no ground-truth trajectory):
   initImuCalibs / ImuExtrinsics   per-IMU variables over the same windows         InitCalibration.cpp:422-579
   initRollingShutterData          per-rig rolling-shutter intervals               InitCalibration.cpp:299-314
   initPointsFromObservations      RANSAC + refinement triangulation (libviba_host) InitPointTracks.cpp:29-63
+                                  (or the `triangulate` provider: engine.triangulate, on the device)
   addVisualFactors                one factor per inlier observation               VisualFactors.cpp:16-62
   regenerateAllPreintegrations... computePreIntegration per rig pair and IMU      InertialFactors.cpp:19-70
   addInertialFactors              consecutive rigs <= 10 s apart                  InertialFactors.cpp:72-100
@@ -186,8 +187,12 @@ def compensated_gyro_at_end(stream, model, t0_us: int, t1_us: int) -> np.ndarray
 
 
 class SessionAdapter:
-    def __init__(self, sd: SessionData, matcher: Matcher, settings: InitSettings | None = None, row_poses=None):
+    def __init__(self, sd: SessionData, matcher: Matcher, settings: InitSettings | None = None, row_poses=None,
+                 triangulate=None):
         self.sd, self.m, self.s = sd, matcher, settings or InitSettings()
+        # triangulatePoint provider: None = the host library (libviba_host, vbh_triangulate); otherwise a function
+        # with the arguments and the return value of engine.triangulate (vb_triangulate_points, on the device)
+        self.triangulate = triangulate
         # T_bodyImu_world_atImageRow provider for the triangulation: the device (engine.rs_row_poses,
         # vb_rs_row_poses) unless a caller passes another implementation with the same arguments
         self.row_poses = row_poses
@@ -325,11 +330,14 @@ class SessionAdapter:
         ok = np.zeros(len(tracks), np.uint8)
         inl = np.zeros(len(flat), np.uint8)
         seeds = np.array(seeds, np.int32)
-        lib = load_host_lib()
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
         Tcw = np.ascontiguousarray(Tcw)
-        lib.vbh_triangulate(len(tracks), ptr(start), ptr(seeds), ptr(Tcw), ptr(camvar), ptr(cams),
-                            ptr(uv), ptr(sh), ptr(pts), ptr(ok), ptr(inl))
+        if self.triangulate is None:
+            lib = load_host_lib()
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+            lib.vbh_triangulate(len(tracks), ptr(start), ptr(seeds), ptr(Tcw), ptr(camvar), ptr(cams),
+                                ptr(uv), ptr(sh), ptr(pts), ptr(ok), ptr(inl))
+        else:
+            pts, ok, inl = self.triangulate(start, seeds, Tcw, camvar, cams, uv, sh)
         # kept for the parity tests (tests/test_session.py against the oracle's triangulatePoint)
         self.triangulation = {"inputs": (start, seeds, Tcw, camvar, cams, uv, sh), "points": pts, "ok": ok,
                               "inliers": inl}
@@ -574,10 +582,12 @@ class SessionAdapter:
 
 
 def build_problem(sd: SessionData, matcher: Matcher | None = None, settings: InitSettings | None = None,
-                  row_poses=None) -> SessionProblem:
+                  row_poses=None, triangulate=None) -> SessionProblem:
     """SessionData -> SessionProblem (ark_vi_ba main_AriaKit_ViBa.cpp:49-63).  row_poses: the
-    T_bodyImu_world_atImageRow provider of the triangulation (default: the device, vb_rs_row_poses)."""
-    return SessionAdapter(sd, matcher or Matcher.build(sd), settings, row_poses).problem()
+    T_bodyImu_world_atImageRow provider of the triangulation (default: the device, vb_rs_row_poses).
+    triangulate: the triangulatePoint provider (default: the host library; engine.triangulate runs it on the
+    device)."""
+    return SessionAdapter(sd, matcher or Matcher.build(sd), settings, row_poses, triangulate).problem()
 
 
 def load_into(engine, p: SessionProblem, finalize: bool = True, recompute_preint: bool | None = None):
@@ -641,19 +651,20 @@ def save_outputs(out_dir: str, engine, p: SessionProblem, sd: SessionData):
 
 def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, settings: InitSettings | None = None,
                 optimizer_settings=None, refine: bool = True, log=print, show_histogram: bool = False,
-                simple_stats: bool = False):
+                simple_stats: bool = False, triangulate=None):
     """ark_vi_ba (interfaces/ark/main_AriaKit_ViBa.cpp:32-133) on a session folder: load, build indices,
     build the problem, rolling-shutter tables, refinePoints, Optimizer::optimize (with the per-iteration
     rolling-shutter rebuild and, under settings.recompute_preint, the preintegration recompute of the
     preStepCallback), then the three output files.  engine_factory(problem) -> engine (default: the HIP
     engine).  show_histogram: log the residual report (report.residual_report: problem.showHistogram,
     main_AriaKit_ViBa.cpp:72,113) after refinePoints and after optimize, when the engine has the report
-    calls.  Returns (engine, problem, summary)."""
+    calls.  triangulate: the triangulatePoint provider of the adapter (None: the host library;
+    engine.triangulate: the device).  Returns (engine, problem, summary)."""
     from .engine import HipEngine, Settings
     s = settings or InitSettings()
     sd = SessionData.load(in_dir, load_imu=True)
     m = Matcher.build(sd)
-    p = SessionAdapter(sd, m, s).problem()
+    p = SessionAdapter(sd, m, s, triangulate=triangulate).problem()
     if log:
         log(f"[ark] {p.summary()}; {p.triangulated} of {p.tried_tracks} tracks triangulated")
     if engine_factory is None:

@@ -37,6 +37,9 @@ void launch_rs_build(const Dev& d, hipStream_t st);
 void launch_rs_row_poses(const Dev& d, int64_t n, const int32_t* obsRig, const int32_t* obsCam, const double* obsRow,
                          const double* rigPose, const double* rigVel, const int32_t* rigRS, const double* cams,
                          double* out, hipStream_t st);
+void launch_triangulate(int64_t nTracks, int64_t nObs, const int64_t* start, const int32_t* seed, const double* Tcw,
+                        const int32_t* obsCam, const double* cams, const double* uv, const double* sqrtH, double* rays,
+                        double* point, uint8_t* ok, uint8_t* inlier, hipStream_t st);
 void launch_preint(const Dev& d, const PreintArgs& pa, hipStream_t st);
 void launch_refine_points(const Dev& d, const int64_t* gStart, const int32_t* gObs, const int32_t* gPt, int64_t nG,
                           double* backups, double* acc, hipStream_t st);

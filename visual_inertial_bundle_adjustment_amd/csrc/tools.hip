@@ -87,6 +87,84 @@ extern "C" int vb_rs_row_poses(int64_t n_imu, const int64_t* imu_t_ns, const dou
   return 0;
 }
 
+// ---------------------------------------------------------------- initial landmark triangulation (session set-up)
+// SingleSessionAdapter::initPointsFromObservations (InitPointTracks.cpp:29-63 -> Triangulation.cpp:34-239) for
+// n_tracks point tracks, the arguments of libviba_host's vbh_triangulate (csrc/session.cpp).  Stateless: one
+// upload of the inputs, the two kernels of triangulate.hip, one download, everything freed.  The arguments are
+// checked on the host before the first HIP call.
+extern "C" int vb_triangulate_points(int64_t n_tracks, const int64_t* start, const int32_t* seed,
+                                     const double* T_cam_world7, const int32_t* obs_cam, int64_t n_cams,
+                                     const double* cams24, const double* uv2, const double* sqrt_h4, double* point3,
+                                     uint8_t* ok, uint8_t* inlier, double* device_ms) {
+  if (n_tracks < 0 || n_cams < 0) return fail(VB_E_ARG, "vb_triangulate_points: negative count");
+  if ((n_cams && !cams24) || (n_tracks && (!start || !seed || !point3 || !ok)))
+    return fail(VB_E_ARG, "vb_triangulate_points: NULL array with a non-zero count");
+  if (start && start[0] != 0) return fail(VB_E_ARG, "vb_triangulate_points: start[0] must be 0");
+  for (int64_t p = 0; p < n_tracks; p++) {
+    if (start[p + 1] < start[p]) return fail(VB_E_ARG, "vb_triangulate_points: start must not decrease");
+    if (start[p + 1] - start[p] > (int64_t)INT32_MAX)
+      return fail(VB_E_ARG, "vb_triangulate_points: a track of 2^31 or more observations");
+  }
+  const int64_t n_obs = n_tracks ? start[n_tracks] : 0;
+  if (n_obs && (!T_cam_world7 || !obs_cam || !uv2 || !sqrt_h4 || !inlier))
+    return fail(VB_E_ARG, "vb_triangulate_points: NULL array with a non-zero count");
+  for (int64_t i = 0; i < n_obs; i++)
+    if (obs_cam[i] < 0 || obs_cam[i] >= n_cams)
+      return fail(VB_E_ARG, "vb_triangulate_points: observation with an unknown camera");
+  for (int64_t c = 0; c < n_cams; c++)
+    if (cams24[24 * c] != (double)VB_CAM_LINEAR && cams24[24 * c] != (double)VB_CAM_FISHEYE624)
+      return fail(VB_E_ARG, "vb_triangulate_points: camera record with an unknown model");
+  if (device_ms) *device_ms = 0.0;
+  if (n_tracks == 0) return 0;
+  std::vector<void*> mem;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  auto freeAll = [&] {
+    for (void* p : mem) (void)hipFree(p);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  };
+  auto up = [&](auto** dst, const auto* src, size_t n) -> bool {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(*src)) != hipSuccess) return false;
+    mem.push_back(p);
+    *dst = (std::remove_cv_t<std::remove_reference_t<decltype(**dst)>>*)p;
+    return n == 0 || hipMemcpy(p, src, n * sizeof(*src), hipMemcpyHostToDevice) == hipSuccess;
+  };
+  auto zero = [&](auto** dst, size_t n) -> bool {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(**dst)) != hipSuccess) return false;
+    mem.push_back(p);
+    *dst = (std::remove_reference_t<decltype(*dst)>)p;
+    return hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(**dst)) == hipSuccess;
+  };
+  int64_t* dStart = nullptr;
+  int32_t *dSeed = nullptr, *dCam = nullptr;
+  double *dT = nullptr, *dCams = nullptr, *dUv = nullptr, *dSh = nullptr, *dRays = nullptr, *dPt = nullptr;
+  uint8_t *dOk = nullptr, *dInl = nullptr;
+  const size_t nt = (size_t)n_tracks, no = (size_t)n_obs;
+  const bool okUp = up(&dStart, start, nt + 1) && up(&dSeed, seed, nt) && up(&dT, T_cam_world7, no * 7) &&
+                    up(&dCam, obs_cam, no) && up(&dCams, cams24, (size_t)n_cams * 24) && up(&dUv, uv2, no * 2) &&
+                    up(&dSh, sqrt_h4, no * 4) && zero(&dRays, no * 6) && zero(&dPt, nt * 3) && zero(&dOk, nt) &&
+                    zero(&dInl, no) && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+  if (!okUp) {
+    freeAll();
+    return fail(VB_E_HIP, "vb_triangulate_points: no HIP device, or device allocation / copy failed");
+  }
+  float ms = 0.f;
+  bool okRun = hipEventRecord(e0, nullptr) == hipSuccess;
+  launch_triangulate(n_tracks, n_obs, dStart, dSeed, dT, dCam, dCams, dUv, dSh, dRays, dPt, dOk, dInl, nullptr);
+  okRun = okRun && hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
+          hipEventSynchronize(e1) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+          hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+          hipMemcpy(point3, dPt, nt * 3 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+          hipMemcpy(ok, dOk, nt, hipMemcpyDeviceToHost) == hipSuccess &&
+          (no == 0 || hipMemcpy(inlier, dInl, no, hipMemcpyDeviceToHost) == hipSuccess);
+  freeAll();
+  if (!okRun) return fail(VB_E_HIP, "vb_triangulate_points: kernel failed");
+  if (device_ms) *device_ms = ms;
+  return 0;
+}
+
 // ---------------------------------------------------------------- kernel micro-benchmark (tuning aid)
 // Times one launch of a factorization kernel on scratch tiles (random SPD diagonal tile, random
 // off-diagonal tiles), averaged over `iters` launches, kernel-exact (hipExtLaunchKernelGGL events).

@@ -108,6 +108,42 @@ def rs_row_poses(imu_t, imu_gyro, imu_accel, rs_mid, rs_half, rs_calib, gravity,
     return out
 
 
+def triangulate(start, seeds, Tcw, camvar, cams, uv, sqrt_h):
+    """initPointsFromObservations on the device (vb_triangulate_points, include/viba_hip.h): triangulatePoint
+    for every track, one wave per track.  Track p owns observations start[p]..start[p + 1] of Tcw (n_obs, 7:
+    T_cam_world at the observation's image row), camvar (camera record of cams, (n_cams, 24)), uv (n_obs, 2) and
+    sqrt_h (n_obs, 4); seeds[p] = pointId + 1729.  Returns (points (n, 3), ok (n,), inlier flags per
+    observation): the signature and the return value of oracle.refcpu.triangulate, so either serves as the
+    adapter's `triangulate` provider.  The kernels' HIP-event time [ms] of the last call is left in
+    `triangulate.last_device_ms`.  Errors raise VbError."""
+    from ._lib import load_hip_lib
+    lib = load_hip_lib()
+    start, seeds = _arr(start, np.int64), _arr(seeds, np.int32)
+    Tcw, cams = _arr(Tcw, np.float64).reshape(-1, 7), _arr(cams, np.float64).reshape(-1, 24)
+    camvar = _arr(camvar, np.int32)
+    uv, sqrt_h = _arr(uv, np.float64).reshape(-1, 2), _arr(sqrt_h, np.float64).reshape(-1, 4)
+    n = max(len(start) - 1, 0)
+    n_obs = int(start[-1]) if len(start) else 0
+    if n_obs < 0 or not (len(seeds) == n and len(Tcw) == len(camvar) == len(uv) == len(sqrt_h) and len(Tcw) >= n_obs):
+        raise VbError(-1, "triangulate: array lengths do not match start")
+    pts, ok, inl = np.zeros((n, 3)), np.zeros(n, np.uint8), np.zeros(n_obs, np.uint8)
+    ms = C.c_double(0.0)
+    f = lib.vb_triangulate_points
+    f.restype = C.c_int
+    f.argtypes = [C.c_int64, P, P, P, P, C.c_int64, P, P, P, P, P, P, C.POINTER(C.c_double)]
+    ptr = lambda a: a.ctypes.data_as(P) if a.size else None
+    rc = f(n, start.ctypes.data_as(P) if n else None, ptr(seeds), ptr(Tcw), ptr(camvar), len(cams), ptr(cams), ptr(uv),
+           ptr(sqrt_h), ptr(pts), ptr(ok), ptr(inl), C.byref(ms))
+    if rc != 0:
+        lib.vb_last_error.restype = C.c_char_p
+        raise VbError(rc, lib.vb_last_error().decode())
+    triangulate.last_device_ms = ms.value
+    return pts, ok, inl
+
+
+triangulate.last_device_ms = None
+
+
 class CEngineBase:
     """Shared ctypes plumbing for engines exposing the vb_* function family under a prefix."""
 
