@@ -417,6 +417,41 @@ int vb_optimize(vb_handle h, const vb_settings* s, vb_log_cb log, vb_prestep_cb 
                 vb_summary* out);
 int vb_last_phase_times(vb_handle h, vb_phase_times* out);
 
+/* The decisions of Optimizer::optimize (Optimizer.cpp:834-1097) alone, over primitives the caller supplies:
+ * vb_optimize and the multi-process controllers (distributed.py) both run this one statement of them.
+ * What one iteration leaves for the decisions (Optimizer.cpp:807-833, 857-897): */
+typedef struct vb_lm_iteration {
+  double prev_cost;       /* cost at the linearization point (:807-815) */
+  double new_cost;        /* comparable cost after the full step (:893-897) */
+  double model_reduction; /* model cost reduction of the full step (:826-833) */
+  double step_rms_ratio;  /* ratioS2Vn2 of the full step's applyStep (:886), read by :1014-1018 */
+  vb_cost_stats stats;    /* CostStats of the full step's cost pass */
+} vb_lm_iteration;
+/* The primitives; each returns 0 or a VB_E_* code, which ends the run and is returned unchanged.
+ *   iteration          everything up to the iteration's costs: linearize (dontRetryFailed), damp + factor +
+ *                      solve at `damping`, backup, applyStep, computeCost (:807-897)
+ *   gradient_dot_step, scale_step, restore, apply_step (ratios discarded, :927, :972), cost (comparable),
+ *   solve_with_new_gradient   as the vb_* calls of these names: the step-rescaling loop (:905-1003)
+ *   step_outcome       (may be NULL) the accept / reject decision is taken (:1019), before the rejected step's
+ *                      restoreVariables (:1026): where a caller drops work queued on the assumption that
+ *                      the full step stays applied
+ *   iteration_done     (may be NULL) the damping is updated and the iteration counted (:1019-1057), `it` the
+ *                      number of iterations done; not called when damping > damping_max ends the run (:1027) */
+typedef struct vb_lm_ops {
+  int (*iteration)(void* user, int it, double damping, int dont_retry_failed, vb_lm_iteration* out);
+  int (*gradient_dot_step)(void* user, int dont_retry_failed, double* back_red);
+  int (*scale_step)(void* user, double factor);
+  int (*restore)(void* user);
+  int (*apply_step)(void* user, int which);
+  int (*cost)(void* user, double* cost, vb_cost_stats* stats);
+  int (*solve_with_new_gradient)(void* user);
+  int (*step_outcome)(void* user, int rejected, int rescaled);
+  int (*iteration_done)(void* user, int it, double prev_cost, double new_cost, double damping, int rescaled);
+} vb_lm_ops;
+/* Optimizer.cpp:834-1097 over `ops` (s == NULL: vb_default_settings).  Host code only: no handle, no HIP call,
+ * vb_last_error untouched.  VB_E_ARG for a NULL table or a NULL primitive other than the two hooks. */
+int vb_lm_run(const vb_settings* s, const vb_lm_ops* ops, void* user, vb_summary* out);
+
 /* applyStep without the normalisation: raw = {max ratio, sum ratio^2, sum ratio} over the variables
  * this handle counts (a shard: its landmarks, + the reduced variables on the root), so that a
  * multi-device caller can reduce them; vb_apply_step = raw normalised by vb_num_params */

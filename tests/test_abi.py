@@ -11,7 +11,8 @@ import subprocess
 import pytest
 
 from visual_inertial_bundle_adjustment_amd import _lib
-from visual_inertial_bundle_adjustment_amd.engine import HipEngine, PhaseTimes, Settings, Summary
+from visual_inertial_bundle_adjustment_amd.engine import (CostStats, HipEngine, LmIteration, LmOps, PhaseTimes, Settings,
+                                                          Summary)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "viba_hip.h")
@@ -51,9 +52,10 @@ def _c_sizes():
 #include <stddef.h>
 #include "{HEADER}"
 int main(void) {{
-  printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(vb_config), sizeof(vb_settings), sizeof(vb_summary),
-         sizeof(vb_cost_stats), sizeof(vb_phase_times), offsetof(vb_settings, damping),
-         offsetof(vb_summary, num_iterations));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(vb_config), sizeof(vb_settings),
+         sizeof(vb_summary), sizeof(vb_cost_stats), sizeof(vb_phase_times), offsetof(vb_settings, damping),
+         offsetof(vb_summary, num_iterations), sizeof(vb_lm_iteration), sizeof(vb_lm_ops),
+         offsetof(vb_lm_iteration, stats), offsetof(vb_lm_ops, iteration_done));
   return 0;
 }}"""
     d = os.path.join(ROOT, "oracle", "_ref")
@@ -65,7 +67,7 @@ int main(void) {{
 
 
 def test_struct_layouts_match_ctypes_mirrors():
-    cfg, st, summ, cs, pt, off_damp, off_it = _c_sizes()
+    cfg, st, summ, cs, pt, off_damp, off_it, lm_it, lm_ops, off_stats, off_done = _c_sizes()
     assert cfg == C.sizeof(HipEngine.Config)
     assert st == C.sizeof(Settings)
     assert summ == C.sizeof(Summary)
@@ -73,6 +75,9 @@ def test_struct_layouts_match_ctypes_mirrors():
     assert pt == C.sizeof(PhaseTimes)
     assert off_damp == Settings.damping.offset
     assert off_it == Summary.num_iterations.offset
+    assert cs == C.sizeof(CostStats)
+    assert lm_it == C.sizeof(LmIteration) and off_stats == LmIteration.stats.offset
+    assert lm_ops == C.sizeof(LmOps) and off_done == LmOps.iteration_done.offset
 
 
 def test_factor_tables_match_header():

@@ -1,10 +1,12 @@
 """The LM controller's variable-tolerance test (Optimizer.cpp:1014-1018) on a rescaled iteration.
 
 `toleranceHit` reads ratioS2Vn2 from the FULL step's applyStep (Optimizer.cpp:886); the rescaled
-attempts' applyStep calls (:927, :972) discard their ratios.  Every controller restates this: the oracle
-(oracle/refcpu.cpp ref_optimize), vb_optimize (api.hip) and the Python controller of the multi-process
-path (distributed.ShardedOptimizer).  The case only shows when a rescaled iteration's full step is above
-`variables_tolerance` and its scaled step below it, with `stop_if_no_improvement_for=1` so that the
+attempts' applyStep calls (:927, :972) discard their ratios.  There are two statements of this: the oracle's
+(oracle/refcpu.cpp ref_optimize) and the package's (csrc/lm_controller.hpp), which vb_optimize
+(optimize.hip) runs over its device-queueing primitives and the multi-process path
+(distributed.ShardedOptimizer, through vb_lm_run) over its collective ones.  The case only shows when
+a rescaled iteration's full step is above `variables_tolerance` and its scaled step below it, with
+`stop_if_no_improvement_for=1` so that the
 tolerance decides the iteration count: `variables_tolerance` is placed between the two, on the first
 iteration, so a controller reading the scaled step's ratio stops after one iteration and one reading the
 full step's goes on.  (Until round 5 the oracle read the scaled one.)
@@ -87,8 +89,9 @@ def _py_worker(rank, world, port, which, settings_bytes, out_dir):
 
 @pytest.mark.parametrize("which", ["A"])
 def test_variable_tolerance_reads_full_step_ratio_cpu(which, tmp_path):
-    """The Python controller (one gloo rank over the oracle's primitives; its loop restates
-    Optimizer.cpp:800-1097 independently of ref_optimize) and ref_optimize give the same trajectory, and
+    """The Python controller (one gloo rank over the oracle's primitives; its decisions are the package's
+    statement of Optimizer.cpp:834-1097, vb_lm_run, independent of ref_optimize) and ref_optimize give the
+    same trajectory, and
     the variable tolerance did not stop the first (rescaled) iteration."""
     from oracle.refcpu import RefEngine
     full = full_step_rms(RefEngine, which)

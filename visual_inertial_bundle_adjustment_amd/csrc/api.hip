@@ -1,7 +1,7 @@
-// Host side of the HIP LM engine: the C-ABI (include/viba_hip.h) numeric phases and the
-// Levenberg-Marquardt controller (≙ Optimizer::optimize, Optimizer.cpp:768-1106).  All numeric work runs
-// in HIP kernels on the handle's stream; the host only orders launches, reads back scalars and takes LM
-// decisions.  vb_finalize's symbolic analysis is finalize.hip, the multi-process entries multi.hip.
+// Host side of the HIP LM engine: the C-ABI (include/viba_hip.h) numeric phases.  All numeric work runs
+// in HIP kernels on the handle's stream; the host only orders launches and reads back scalars.  The
+// Levenberg-Marquardt loop (vb_optimize ≙ Optimizer::optimize, Optimizer.cpp:768-1106) is optimize.hip over
+// lm_controller.hpp, vb_finalize's symbolic analysis finalize.hip, the multi-process entries multi.hip.
 #include "host.hpp"
 
 namespace viba {
@@ -955,7 +955,7 @@ int clearReduced(vb_handle h, const Dev& d, hipStream_t zs) {
 // reduction / error slots (the caller's); events evA / evB bracket it.  early: the small factors'
 // evaluation and the clear were queued on stZ already (specEarly)
 int linearizeBody(vb_handle h, const Dev& d, int update_cache, int dont_retry_failed, hipEvent_t evA, hipEvent_t evB,
-                  bool early = false) {
+                  bool early) {
   const bool fuseCost = d.costS != nullptr;
   HIPCHK(hipEventRecord(evA, h->st));
   // the reduced system is cleared and the small factors assembled on the side stream while the visual
@@ -1402,352 +1402,6 @@ int vb_reduced_buffers(vb_handle h, double** matrix, int64_t* matrix_len, double
   if (matrix_len) *matrix_len = h->d.nTiles * TS * TS;
   if (rhs) *rhs = h->d.rhs;
   if (rhs_len) *rhs_len = (int64_t)h->d.nT * TS;
-  return 0;
-}
-
-// ---- vb_optimize's speculative linearization of the next iteration (vb_handle_s::tilesAlt ..)
-// Frees whatever specPrepare got before a failure (nothing has been swapped into h->d then).
-void specRelease(vb_handle h) {
-  for (void* p : {(void*)h->tilesAlt, (void*)h->cacheAlt, (void*)h->gRedAlt, (void*)h->rsSAlt, (void*)h->rsIAlt,
-                  (void*)h->rsGAlt, (void*)h->rsNAlt})
-    if (p) (void)hipFree(p);
-  h->tilesAlt = h->cacheAlt = h->gRedAlt = h->rsSAlt = h->rsIAlt = h->rsGAlt = nullptr;
-  h->rsNAlt = nullptr;
-  for (auto& row : h->evS)
-    for (hipEvent_t& e : row)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-  if (h->evCost) (void)hipEventDestroy(h->evCost), h->evCost = nullptr;
-  if (h->stR) (void)hipStreamDestroy(h->stR), h->stR = nullptr;
-  if (h->hostRed) (void)hipHostFree(h->hostRed), h->hostRed = nullptr;
-  (void)hipGetLastError();
-}
-// The spare tile store (nTiles x 32 KB: 2.2 GB at config C), ResultCache, gradient and rolling-shutter
-// tables of the speculative linearization, allocated at the first vb_optimize that speculates.  Returns
-// false when any of it cannot be had: the caller then runs the plain controller (no speculation), as
-// before the speculative path existed, instead of failing a problem that fits without it.
-bool specPrepare(vb_handle h) {
-  if (h->specReady) return true;
-  Dev& d = h->d;
-  bool ok = !alloc0(&h->tilesAlt, (size_t)d.nTiles * TS * TS) && !alloc0(&h->cacheAlt, d.nObs) &&
-            !alloc0(&h->gRedAlt, (size_t)d.nT * TS) && !h->specFailDebug;
-  if (ok && h->rsDevice) {
-    const int64_t ns = h->rsOff[h->nRS];
-    ok = !alloc0(&h->rsSAlt, ns * 11) && !alloc0(&h->rsIAlt, (ns - h->nRS) * 9) &&
-         !alloc0(&h->rsGAlt, (size_t)h->nRS * 3) && !alloc0(&h->rsNAlt, h->nRS);
-  }
-  for (auto& row : h->evS)
-    for (hipEvent_t& e : row) ok = ok && hipEventCreate(&e) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&h->evCost, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipStreamCreateWithFlags(&h->stR, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&h->hostRed, 32 * sizeof(double), hipHostMallocDefault) == hipSuccess;
-  if (!ok) specRelease(h);
-  h->specReady = ok;
-  return ok;
-}
-// the buffers the speculative work writes instead of h->d's
-Dev specDev(vb_handle h) {
-  Dev ds = h->d;
-  ds.tiles = h->tilesAlt, ds.cacheW = h->cacheAlt, ds.gRed = h->gRedAlt;
-  ds.red = h->d.red + 48, ds.err = h->d.err + 4;
-  ds.redS = h->d.redS + 64 * 8;  // own stripes: the fused cost pass adds into the handle's (costS)
-  if (h->rsDevice) ds.rsS = h->rsSAlt, ds.rsI = h->rsIAlt, ds.rsG = h->rsGAlt, ds.rsN = h->rsNAlt;
-  return ds;
-}
-// ark_vi_ba's preStepCallback (the rolling-shutter rebuild at the accepted variables) and the
-// linearization of the next iteration, queued behind this iteration's cost pass; event set p
-// With early set, specEarly queued the small factors' evaluation and the clear beside the cost pass.
-// rsDone: vb_optimize already cleared the speculative slots and queued the rebuild on stF (evRs), beside
-// the cost pass; the main stream only waits for it.
-int specEnqueue(vb_handle h, int dontRetry, int p, bool early, bool rsDone, bool fuseCost) {
-  Dev ds = specDev(h);
-  if (fuseCost) ds.costS = h->d.redS;
-  if (!early && !rsDone) {
-    HIPCHK(hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->st));
-    HIPCHK(hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->st));
-  }
-  if (rsDone) {
-    HIPCHK(hipStreamWaitEvent(h->st, h->evRs, 0));
-  } else {
-    HIPCHK(hipEventRecord(h->evS[p][0], h->st));
-    if (h->rsDevice) launch_rs_build(ds, h->st);
-    HIPCHK(hipEventRecord(h->evS[p][1], h->st));
-  }
-  return linearizeBody(h, ds, 1, dontRetry, h->evS[p][2], h->evS[p][3], early);
-}
-// The part of the speculative linearization that needs only the stepped variables, queued on stZ after
-// the box-plus so it runs beside the cost pass (which leaves the HBM and most CUs idle): the small
-// factors' evaluation into the staging slots and the clear of the spare tile store and gradient.  The
-// staging slots are free there (the iteration's assembly is joined, and vb_gradient_dot_step's
-// evaluation forks from the main stream after the speculative linearization's join).
-int specEarly(vb_handle h, bool cleared, bool storeCleared) {
-  if (!smallHere(h, 0)) return 0;
-  const Dev ds = specDev(h);
-  if (!cleared) {
-    HIPCHK(hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->st));
-    HIPCHK(hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->st));
-  }
-  HIPCHK(hipEventRecord(h->evFork, h->st));
-  HIPCHK(hipStreamWaitEvent(h->stZ, h->evFork, 0));
-  if (storeCleared && h->clearOnF) HIPCHK(hipStreamWaitEvent(h->stZ, h->evClrDone, 0));
-  launch_small_eval(ds, 0, ds.gRed, h->stZ);
-  // (storeCleared: the factorization queued the clear on stZ already, factorSeqSn)
-  return storeCleared ? 0 : clearReduced(h, ds, h->stZ);
-}
-// the step was accepted at full size: the speculative buffers become the handle's
-void specCommit(vb_handle h) {
-  Dev& d = h->d;
-  std::swap(d.tiles, h->tilesAlt);
-  std::swap(d.cache, h->cacheAlt);
-  d.cacheW = d.cache;
-  std::swap(d.gRed, h->gRedAlt);
-  if (h->rsDevice) {
-    std::swap(d.rsS, h->rsSAlt), std::swap(d.rsI, h->rsIAlt);
-    std::swap(d.rsG, h->rsGAlt), std::swap(d.rsN, h->rsNAlt);
-  }
-  h->tileSet ^= 1;
-  launch_spec_commit(d, h->st);
-}
-// the iteration's scalars red[0, n) and error words, read on the readback stream once the cost pass
-// (evCost) is done, while whatever was queued behind it runs
-int readIterScalars(vb_handle h, double* out, int n) {
-  HIPCHK(hipStreamWaitEvent(h->stR, h->evCost, 0));
-  HIPCHK(hipMemcpyAsync(h->hostRed, h->d.red, n * sizeof(double), hipMemcpyDeviceToHost, h->stR));
-  HIPCHK(hipMemcpyAsync(h->hostRed + 24, h->d.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stR));
-  HIPCHK(hipStreamSynchronize(h->stR));
-  std::copy(h->hostRed, h->hostRed + n, out);
-  h->profDone = h->profAtCost;
-  int32_t ee[2];
-  std::memcpy(ee, h->hostRed + 24, sizeof(ee));
-  return errFromWords(h, ee);
-}
-
-// Optimizer::optimize (Optimizer.cpp:768-1106).  Per iteration the linearization, damp + eliminate +
-// factor + solve, backup, box-plus and cost pass are queued back to back and the host reads their
-// scalars once.  Unless a prestep callback or --recompute-preint needs the host between iterations, the
-// next iteration's rolling-shutter rebuild and linearization are queued speculatively behind the cost
-// pass (into second buffers, specEnqueue), so the device works while the host decides; they are used
-// when the step is accepted at full size, the common case.  An error after the backup restores the
-// variables of the iteration's linearization point before returning.
-int vb_optimize(vb_handle h, const vb_settings* sp, vb_log_cb log, vb_prestep_cb pre, void* user, vb_summary* out) {
-  if (!h || !h->finalized) return fail(VB_E_STATE, "vb_optimize before vb_finalize");
-  vb_settings s;
-  if (sp) s = *sp;
-  else vb_default_settings(&s);
-  double damping = s.damping;
-  int it = 0, lastImpr = 0, lastTroubled = -10;
-  double initialCost = 0, finalCost = 0, troubledStartDamping = damping;
-  int troubledStart = 0, nTroubled = 0, largestTroubled = 0, nRescaled = 0;
-  int dontRetry = 0;
-  auto acceptable = [](const vb_cost_stats& st) {
-    const double rate = st.num_invalid / (st.num_total + 1.0);
-    return rate < 0.03 && (st.num_invalid < st.num_prev_invalid * 2.0 + 50);
-  };
-  const bool preint = h->recomputePreint && h->pi.n > 0;
-  // (no memory for the spare buffers: the plain controller, which needs none)
-  const bool speculate = !pre && !preint && !h->sharded && !h->partSet && specPrepare(h);
-  bool specQueued = false;  // the current iteration's rebuild + linearization were queued speculatively
-  int specSet = 0;
-  int rc;
-  char buf[512];
-  // an error after this iteration's backup: the variables go back to the linearization point
-  bool backedUp = false;
-  auto bail = [&](int code) {
-    if (backedUp && vb_restore(h) == 0) (void)hipStreamSynchronize(h->st);
-    (void)hipStreamSynchronize(h->st);
-    return code;
-  };
-  while (true) {
-    auto t0 = std::chrono::steady_clock::now();
-    backedUp = false;
-    if (specQueued) {
-      specCommit(h);
-    } else {
-      // ark_vi_ba's preStepCallback (main_AriaKit_ViBa.cpp:95-101): updateRollingShutterData
-      // and, under --recompute-preint, the preintegrations from the IMU streams (InertialFactors.cpp:19-70)
-      if ((h->rsDevice || preint) && (rc = rsUpdateAsync(h, h->rsDevice, preint))) return bail(rc);
-      if (pre) pre(it, user);
-      if ((rc = linearizeEnqueue(h, 1, dontRetry))) return bail(rc);
-    }
-    // damp + eliminate + factor + solve, backup, box-plus and the cost pass queued back to back; the host
-    // reads their scalars (costs, CostStats, model reduction, step ratios) and errors once, after the cost
-    // pass: none of them changes what the queued work does
-    double prevCost, modelRed, ratios[3], newCost;
-    vb_cost_stats st;
-    const bool specNext = speculate && it + 1 < s.max_num_iterations;
-    const bool early = specNext && smallHere(h, 0) && h->specEarly;
-    h->clearWanted = early && h->clearInFactor, h->clearQueued = false;
-    rc = dampFactorSolveEnqueue(h, damping, false);
-    const bool storeCleared = h->clearQueued;
-    h->clearWanted = h->clearQueued = false;
-    if (rc) return bail(rc);
-    if ((rc = vb_backup(h))) return bail(rc);
-    backedUp = true;
-    if ((rc = applyStepEnqueue(h, 0, 10, 11))) return bail(rc);
-    // the next iteration's rolling-shutter rebuild (a few latency-bound waves) on stF beside the cost pass
-    // instead of after it on the main stream: the speculative slots are cleared first (the rebuild sets
-    // error bits), and the main stream waits for it (evRs) before the linearization -- and so before
-    // anything the host queues after its read, e.g. a restore of the variables the rebuild reads
-    bool rsSide = false;
-    if (specNext && h->rsDevice) {
-      const Dev ds = specDev(h);
-      const int p = specSet ^ 1;
-      if (hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->st) != hipSuccess ||
-          hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->st) != hipSuccess ||
-          hipEventRecord(h->evStep, h->st) != hipSuccess || hipStreamWaitEvent(h->stF, h->evStep, 0) != hipSuccess ||
-          hipEventRecord(h->evS[p][0], h->stF) != hipSuccess)
-        return bail(fail(VB_E_HIP, "speculative rebuild fork"));
-      launch_rs_build(ds, h->stF);
-      if (hipEventRecord(h->evS[p][1], h->stF) != hipSuccess || hipEventRecord(h->evRs, h->stF) != hipSuccess)
-        return bail(fail(VB_E_HIP, "speculative rebuild join"));
-      rsSide = true;
-    }
-    if (early && (rc = specEarly(h, rsSide, storeCleared))) return bail(rc);
-    // the global-shutter part of the cost pass inside the speculative linearization (every observation
-    // evaluated there: not under dontRetry)
-    const bool fuseCost = specNext && h->costFuse && !dontRetry;
-    if ((rc = fuseCost ? costFusedEnqueue(h) : costEnqueue(h, 1, false))) return bail(rc);
-    const bool wasSpec = specQueued;
-    const int wasSet = specSet;
-    specQueued = false;
-    if (speculate) {
-      if (!fuseCost) {  // (fused: recorded after the speculative visual linearization)
-        if (hipEventRecord(h->evCost, h->st) != hipSuccess) return bail(fail(VB_E_HIP, "hipEventRecord"));
-        h->profAtCost = h->profUsed;
-      }
-      // the next iteration's rebuild + linearization, assuming this step is accepted at full size (not
-      // after the last iteration: its work would only be discarded)
-      if (it + 1 < s.max_num_iterations) {
-        specSet ^= 1;
-        if ((rc = specEnqueue(h, dontRetry, specSet, early, rsSide, fuseCost))) return bail(rc);
-        specQueued = true;
-      }
-    }
-    profHarvestPrefix(h, h->profDone);  // the previous iteration's event times, read while this one runs
-    {
-      double r[17];
-      if ((rc = speculate ? readIterScalars(h, r, 17) : readRedErr(h, r, 17))) return bail(rc);
-      if (it == h->faultFailIt) return bail(fail(VB_E_NUMERIC, "reduced system Cholesky breakdown (injected)"));
-      prevCost = r[0], modelRed = 0.5 * r[16];
-      const double n = (double)std::max<int64_t>(1, h->nParams);
-      ratios[0] = r[8], ratios[1] = std::sqrt(r[9] / n), ratios[2] = r[10] / n;
-      costStats(h, r + 1, &newCost, &st);
-      if (wasSpec) {
-        h->times.linearize_ms = elapsed(h->evS[wasSet][2], h->evS[wasSet][3]);
-        if (h->rsDevice) h->times.rs_update_ms = elapsed(h->evS[wasSet][0], h->evS[wasSet][1]);
-      } else {
-        h->times.linearize_ms = elapsed(h->ev[0], h->ev[1]);
-        if (h->rsTimed) h->times.rs_update_ms = elapsed(h->ev[8], h->ev[9]), h->rsTimed = false;
-      }
-      h->times.schur_ms = elapsed(h->ev[2], h->ev[3]);
-      h->times.factor_ms = elapsed(h->ev[3], h->ev[4]);
-      h->times.solve_ms = elapsed(h->ev[4], h->ev[5]);
-      h->times.step_ms = elapsed(h->ev[10], h->ev[11]);
-      h->times.cost_ms = elapsed(h->ev[6], h->ev[7]);
-      h->linearized = false, h->factored = true;
-    }
-    finalCost = prevCost;
-    if (it == 0) initialCost = prevCost;
-    if (it == h->faultNegModelRedIt) modelRed = -modelRed;  // test fault injection
-    if (modelRed < 0) {
-      // Optimizer.cpp:835-854: the reference re-linearizes into `hess` at the same point (the caches
-      // and the gradient it recomputes are the ones it has) and raises the damping, keeping the old
-      // step.  Its re-linearization also overwrites the factor in `hess`, so a later sub-step solve
-      // of that iteration runs BaSpaCho's triangular solves on an unfactored matrix; that value is
-      // defined by BaSpaCho's storage layout and is not reproduced: here the sub-step uses the
-      // factor (tests/test_parity_configs.py forces this branch).
-      damping *= s.damping_adjust_on_fail;
-    }
-    double costRed = prevCost - newCost;
-    const double ratioRedToCost = costRed / newCost;
-    double ratioRedToExp = costRed / modelRed;
-    double applied = 1.0;
-    bool okRate = acceptable(st);
-    bool rescaled = false;
-    if (s.max_step_factor_attempts > 0 && (ratioRedToExp < s.min_relative_cost_reduction || !okRate)) {
-      rescaled = true, nRescaled++;
-      double backRed;
-      if ((rc = vb_gradient_dot_step(h, dontRetry, &backRed))) return bail(rc);
-      double sf = backRed > 0 ? modelRed / (modelRed + backRed) : s.step_factor_decrease;
-      for (int i = 0; i < s.max_step_factor_attempts; i++) {
-        applied *= sf;
-        if ((rc = vb_scale_step(h, sf)) || (rc = vb_restore(h))) return bail(rc);
-        double rr[3];
-        if ((rc = vb_apply_step(h, 0, rr))) return bail(rc);
-        vb_cost_stats stF;
-        double costF;
-        if ((rc = vb_cost(h, 1, &costF, &stF))) return bail(rc);
-        const double redF = prevCost - newCost;  // Optimizer.cpp:935 (reference uses the full-step cost)
-        const double rF = redF / (modelRed * applied);
-        if (rF >= s.min_relative_cost_reduction && acceptable(stF)) {
-          newCost = costF, st = stF, costRed = redF, ratioRedToExp = rF, okRate = true;
-          break;
-        }
-        if (s.try_sub_step) {
-          double br;
-          if ((rc = vb_gradient_dot_step(h, dontRetry, &br))) return bail(rc);
-          if ((rc = vb_solve_with_new_gradient(h))) return bail(rc);
-          double r2[3];
-          if ((rc = vb_apply_step(h, 1, r2))) return bail(rc);
-          vb_cost_stats stS;
-          double costS;
-          if ((rc = vb_cost(h, 1, &costS, &stS))) return bail(rc);
-          const double redS = prevCost - costS;
-          const double rS = redS / (modelRed * applied);
-          if (rS >= s.min_relative_cost_reduction && acceptable(stS)) {
-            newCost = costS, st = stS, costRed = redS, ratioRedToExp = rS, okRate = true;
-            break;
-          }
-        }
-        dontRetry = 1;
-        sf = s.step_factor_decrease;
-      }
-    }
-    const char* tol = ratioRedToCost < s.relative_cost_tolerance     ? "relative cost"
-                      : costRed < s.absolute_cost_tolerance          ? "absolute cost"
-                      : ratios[1] < s.variables_tolerance            ? "variable"
-                                                                     : nullptr;
-    const bool rejected = newCost > prevCost || !okRate;
-    // the speculative linearization assumed the full step stays applied
-    if (rejected || rescaled) specQueued = false;
-    if (rejected) {
-      if (lastTroubled != it - 1) troubledStartDamping = damping, troubledStart = it;
-      damping *= s.damping_adjust_on_fail;
-      if ((rc = vb_restore(h))) return bail(rc);
-      if (damping > s.damping_max) break;
-      lastTroubled = it;
-    } else {
-      if (lastTroubled == it - 1)
-        if (troubledStartDamping < 1e1 && damping > 1e-3) {
-          nTroubled++;
-          largestTroubled = std::max(largestTroubled, it - troubledStart);
-        }
-      if (ratioRedToExp >= s.min_relative_cost_reduction && applied > s.min_step_factor_for_good)
-        damping = std::max(damping * s.damping_adjust_on_good_step, s.damping_min);
-      else
-        damping *= s.damping_adjust_on_average_step;
-      finalCost = newCost;
-    }
-    h->times.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    it++;
-    if (log && s.verbose) {
-      snprintf(buf, sizeof(buf),
-               "it %d cost %.12g -> %.12g lambda %.3g (t %.2f ms: lin %.2f schur %.2f factor %.2f solve %.2f)", it,
-               prevCost, newCost, damping, h->times.total_ms, h->times.linearize_ms, h->times.schur_ms,
-               h->times.factor_ms, h->times.solve_ms);
-      log(buf, user);
-    }
-    if (!tol) lastImpr = it;
-    if (it >= lastImpr + s.stop_if_no_improvement_for && it >= lastTroubled + s.distance_from_troubled_iteration) break;
-    if (it >= s.max_num_iterations) break;
-  }
-  // (a speculative linearization left queued by a convergence stop is never committed; its buffers are
-  // the spare ones)
-  HIPCHK(hipStreamSynchronize(h->st));
-  if (out) {
-    out->initial_cost = initialCost, out->final_cost = finalCost;
-    out->num_troubled_seqs = nTroubled, out->largest_troubled_seq = largestTroubled, out->num_iterations = it;
-    out->num_rescaled = nRescaled;
-  }
   return 0;
 }
 

@@ -1,5 +1,5 @@
 // Declarations of the host functions the engine's translation units share (host.hpp): api.hip defines
-// all but doFinalize (finalize.hip).
+// all but doFinalize (finalize.hip) and vb_optimize's speculation (optimize.hip).
 #pragma once
 
 namespace viba_host {
@@ -7,6 +7,7 @@ namespace viba_host {
 float profPairMs(hipEvent_t a, hipEvent_t b);
 double elapsed(hipEvent_t a, hipEvent_t b);
 void profHarvest(vb_handle h);
+void profHarvestPrefix(vb_handle h, size_t n);
 int checkErr(vb_handle h);
 int errFromWords(vb_handle h, const int32_t* ee);
 int readRed(vb_handle h, double* out, int i0, int n);
@@ -23,15 +24,20 @@ void reportFree(vb_handle h);
 }  // namespace viba_host
 
 extern "C" {
-// queued phases and vb_optimize's speculation (api.hip; C linkage, defined in its C-ABI block)
+// queued phases (api.hip; C linkage, defined in its C-ABI block)
 int clearReduced(vb_handle h, const Dev& d, hipStream_t zs);
-Dev specDev(vb_handle h);
 int rsUpdateAsync(vb_handle h, bool tables = true, bool preint = false);
+int linearizeBody(vb_handle h, const Dev& d, int update_cache, int dont_retry_failed, hipEvent_t evA, hipEvent_t evB,
+                  bool early = false);
 int linearizeEnqueue(vb_handle h, int update_cache, int dont_retry_failed);
 int assembleEnqueue(vb_handle h, double lambda);
 int dampFactorSolveEnqueue(vb_handle h, double lambda, bool clearErr);
 int applyStepEnqueue(vb_handle h, int which, int e0, int e1);
 int costEnqueue(vb_handle h, int comparable, bool clearErr);
+int costFusedEnqueue(vb_handle h);
+void costStats(vb_handle h, const double* r, double* cost, vb_cost_stats* stats);
+// vb_optimize's speculation (optimize.hip)
+Dev specDev(vb_handle h);
 bool specPrepare(vb_handle h);
 void specRelease(vb_handle h);
 int specEnqueue(vb_handle h, int dontRetry, int p, bool early, bool rsDone = false, bool fuseCost = false);

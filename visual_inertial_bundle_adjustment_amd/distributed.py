@@ -19,8 +19,8 @@ stream (deferred mode, vb_set_deferred) and the host reads the LM scalars ONCE:
   8. cost pass (partial cost + CostStats)
   9. the partial scalars of 1, 6, 7, 8 all-reduced in place on the engine stream, then the next
      iteration's linearization queued speculatively (vb_spec_linearize), then one host read
-The LM decisions (Optimizer.cpp:834-1097, restated by vb_optimize) run identically on every rank from
-the reduced scalars.  The bad-step path (step rescale, sub-step with the existing factor) reads its
+The LM decisions (Optimizer.cpp:834-1097: csrc/lm_controller.hpp through vb_lm_run, the one statement
+vb_optimize runs too) run identically on every rank from the reduced scalars.  The bad-step path (step rescale, sub-step with the existing factor) reads its
 scalars phase by phase, as the reference does (vb_gradient_dot_step partial scalar; vb_assemble_new_rhs
 -> reduce -> root vb_solve_reduced -> broadcast -> vb_back_substitute_which(1)), and drops the
 speculative linearization.
@@ -45,7 +45,8 @@ import time
 
 import numpy as np
 
-from .engine import Settings, Summary
+from ._lib import load_hip_lib
+from .engine import CostStats, LmOps, Settings, Summary, VbError
 
 
 # ------------------------------------------------------------------ buffers as torch tensors
@@ -283,9 +284,43 @@ class _IterScalars:
         return v
 
 
+# ------------------------------------------------------------------ the LM decisions (vb_lm_run)
+def lm_run(s: Settings, **ops) -> Summary:
+    """vb_lm_run (csrc/lm_controller.hpp, the LM decisions vb_optimize runs) over Python callables, named as
+    the members of vb_lm_ops and taking their arguments without `user` (outputs through the ctypes pointers).
+    A callable reports failure by raising: the exception is kept, its code (a VbError's own) stops the run, and
+    it is raised again here unchanged."""
+    raised = []
+
+    def guarded(f):
+        def call(_user, *args):
+            try:
+                f(*args)
+                return 0
+            except BaseException as ex:  # must not unwind through the C frames
+                raised.append(ex)
+                return ex.code if isinstance(ex, VbError) and ex.code else -1
+        return call
+    # (the table refers to the CFUNCTYPE objects for the duration of the call)
+    table = LmOps(**{name: t(guarded(ops[name])) for name, t in LmOps._fields_ if name in ops})
+    fn = load_hip_lib().vb_lm_run
+    fn.argtypes = [C.POINTER(Settings), C.POINTER(LmOps), C.c_void_p, C.POINTER(Summary)]
+    fn.restype = C.c_int
+    out = Summary()
+    rc = fn(C.byref(s), C.byref(table), None, C.byref(out))
+    if raised:
+        raise raised[0]
+    if rc:
+        raise VbError(rc, "vb_lm_run: incomplete table of primitives")
+    return out
+
+
 # ------------------------------------------------------------------ the sharded LM controller
 class ShardedOptimizer:
-    """Optimizer::optimize (Optimizer.cpp:768-1106) over landmark shards; mirrors vb_optimize."""
+    """Optimizer::optimize (Optimizer.cpp:768-1106) over landmark shards: the collective half of the loop --
+    one queued iteration whose scalars are reduced over the ranks and read once, and the collective
+    primitives of the bad-step path -- under the LM decisions of csrc/lm_controller.hpp (vb_lm_run), the
+    statement vb_optimize runs."""
 
     def __init__(self, engine, comm: ShardComm):
         self.e, self.c = engine, comm
@@ -393,12 +428,6 @@ class ShardedOptimizer:
     def _optimize(self, s: Settings | None = None) -> Summary:
         s = s or Settings.default()
         e = self.e
-        damping = s.damping
-        it, last_impr, last_troubled = 0, 0, -10
-        initial_cost = final_cost = 0.0
-        troubled_start_damping, troubled_start, n_troubled, largest_troubled = damping, 0, 0, 0
-        n_rescaled = 0
-        dont_retry = False
         deferred = hasattr(e, "set_deferred")
         sc = _IterScalars(e, self.c)
         self.spec_used = sc.spec
@@ -407,140 +436,88 @@ class ShardedOptimizer:
         self.reads_per_iteration = []
         reads0 = self.c.host_reads
 
-        def acceptable(st):
-            rate = st[1] / (st[0] + 1.0)
-            return rate < 0.03 and st[1] < st[2] * 2.0 + 50
+        def iteration(it, damping, dont_retry, out):
+            # ---- queued: linearize, damp + eliminate + exchange + factor + solve, backup, box-plus,
+            # cost pass; their scalars reduced over the ranks and read once (vb_optimize's pattern)
+            nonlocal spec_pending
+            dont_retry = bool(dont_retry)
+            if deferred:
+                e.set_deferred(True)
+            used_spec = spec_pending
+            if spec_pending:
+                e.spec_commit(True)  # the step stayed applied at full size: its linearization is ready
+                spec_pending = False
+            else:
+                self.phases.mark("rs_update_ms")
+                if getattr(e, "rs_device", False):  # ark_vi_ba's preStepCallback (as vb_optimize)
+                    e.update_rs_tables()
+                self.phases.mark("linearize_ms")
+                sc.set(0, e.linearize(True, dont_retry))
+            sc.set(16, 2.0 * self.factor_solve_partial(damping))
+            e.backup()
+            self.phases.mark("step_ms")
+            for i, x in zip((8, 9, 10), e.apply_step_raw(0)):
+                sc.set(i, x)
+            self.phases.mark("cost_ms")
+            cost, st = e.cost(True)
+            sc.set(1, cost)
+            for i, x in zip((2, 3, 4), st):
+                sc.set(i, x)
+            self.phases.mark(None)
+            speculate = sc.spec and it + 1 < s.max_num_iterations
+
+            def queue_spec():
+                self.phases.mark("spec_linearize_ms")
+                e.spec_linearize(dont_retry)
+                self.phases.mark(None)
+            v = sc.read(queue_spec if speculate else None)
+            spec_pending = speculate
+            if used_spec and hasattr(e, "spec_phase_ms"):
+                # this iteration's rebuild + linearization ran in the previous iteration's queue: their
+                # own device events (complete: they precede the cost pass just read), as vb_optimize
+                rs_ms, lin_ms = e.spec_phase_ms()
+                self.phases.add("rs_update_ms", rs_ms)
+                self.phases.add("linearize_ms", lin_ms)
+            if deferred:
+                e.set_deferred(False)
+            self.phases.close_iteration()
+            r = out[0]
+            r.prev_cost, r.new_cost, r.model_reduction = v[0], v[1], 0.5 * v[16]
+            r.step_rms_ratio = math.sqrt(v[9] / max(1, self.n_params))
+            r.stats = CostStats(int(round(v[2])), int(round(v[3])), int(round(v[4])))
+
+        def gradient_dot_step(dont_retry, back_red):
+            back_red[0] = self.gradient_dot_step(bool(dont_retry))
+
+        def cost(cost, stats):
+            cost[0], st = self.cost(True)
+            stats[0] = CostStats(*st)
+
+        def step_outcome(rejected, rescaled):
+            nonlocal spec_pending
+            if spec_pending and (rejected or rescaled):  # it assumed the full step stays applied
+                e.spec_commit(False)
+                spec_pending = False
+
+        def iteration_done(it, prev_cost, new_cost, damping, rescaled):
+            nonlocal reads0
+            self.reads_per_iteration.append((self.c.host_reads - reads0, bool(rescaled)))
+            reads0 = self.c.host_reads
 
         try:
-            while True:
-                # ---- queued: linearize, damp + eliminate + exchange + factor + solve, backup, box-plus,
-                # cost pass; their scalars reduced over the ranks and read once (vb_optimize's pattern)
-                if deferred:
-                    e.set_deferred(True)
-                used_spec = spec_pending
-                if spec_pending:
-                    e.spec_commit(True)  # the step stayed applied at full size: its linearization is ready
-                    spec_pending = False
-                else:
-                    self.phases.mark("rs_update_ms")
-                    if getattr(e, "rs_device", False):  # ark_vi_ba's preStepCallback (as vb_optimize)
-                        e.update_rs_tables()
-                    self.phases.mark("linearize_ms")
-                    sc.set(0, e.linearize(True, dont_retry))
-                sc.set(16, 2.0 * self.factor_solve_partial(damping))
-                e.backup()
-                self.phases.mark("step_ms")
-                for i, x in zip((8, 9, 10), e.apply_step_raw(0)):
-                    sc.set(i, x)
-                self.phases.mark("cost_ms")
-                cost, st = e.cost(True)
-                sc.set(1, cost)
-                for i, x in zip((2, 3, 4), st):
-                    sc.set(i, x)
-                self.phases.mark(None)
-                speculate = sc.spec and it + 1 < s.max_num_iterations
-
-                def queue_spec():
-                    self.phases.mark("spec_linearize_ms")
-                    e.spec_linearize(dont_retry)
-                    self.phases.mark(None)
-                v = sc.read(queue_spec if speculate else None)
-                spec_pending = speculate
-                if used_spec and hasattr(e, "spec_phase_ms"):
-                    # this iteration's rebuild + linearization ran in the previous iteration's queue: their
-                    # own device events (complete: they precede the cost pass just read), as vb_optimize
-                    rs_ms, lin_ms = e.spec_phase_ms()
-                    self.phases.add("rs_update_ms", rs_ms)
-                    self.phases.add("linearize_ms", lin_ms)
-                if deferred:
-                    e.set_deferred(False)
-                self.phases.close_iteration()
-                n = max(1, self.n_params)
-                prev_cost, new_cost, model_red = v[0], v[1], 0.5 * v[16]
-                st = (int(round(v[2])), int(round(v[3])), int(round(v[4])))
-                ratios = (v[8], math.sqrt(v[9] / n), v[10] / n)
-                # ---- the LM decisions (Optimizer.cpp:834-1097), identical on every rank
-                final_cost = prev_cost
-                if it == 0:
-                    initial_cost = prev_cost
-                if model_red < 0:  # Optimizer.cpp:835-854 (see vb_optimize)
-                    damping *= s.damping_adjust_on_fail
-                cost_red = prev_cost - new_cost
-                ratio_red_to_cost = cost_red / new_cost
-                ratio_red_to_exp = cost_red / model_red
-                applied = 1.0
-                ok_rate = acceptable(st)
-                rescaled = False
-                if s.max_step_factor_attempts > 0 and (ratio_red_to_exp < s.min_relative_cost_reduction or not ok_rate):
-                    rescaled, n_rescaled = True, n_rescaled + 1
-                    back_red = self.gradient_dot_step(dont_retry)
-                    sf = model_red / (model_red + back_red) if back_red > 0 else s.step_factor_decrease
-                    for _ in range(s.max_step_factor_attempts):
-                        applied *= sf
-                        e.scale_step(sf)
-                        e.restore()
-                        self.apply_step(0)  # (its ratios are discarded, Optimizer.cpp:927)
-                        cost_f, st_f = self.cost(True)
-                        red_f = prev_cost - new_cost  # Optimizer.cpp:935
-                        r_f = red_f / (model_red * applied)
-                        if r_f >= s.min_relative_cost_reduction and acceptable(st_f):
-                            new_cost, st, cost_red, ratio_red_to_exp, ok_rate = cost_f, st_f, red_f, r_f, True
-                            break
-                        if s.try_sub_step:
-                            self.gradient_dot_step(dont_retry)
-                            self.solve_with_new_gradient()
-                            self.apply_step(1)
-                            cost_s, st_s = self.cost(True)
-                            red_s = prev_cost - cost_s
-                            r_s = red_s / (model_red * applied)
-                            if r_s >= s.min_relative_cost_reduction and acceptable(st_s):
-                                new_cost, st, cost_red, ratio_red_to_exp, ok_rate = cost_s, st_s, red_s, r_s, True
-                                break
-                        dont_retry = True
-                        sf = s.step_factor_decrease
-                tol = (ratio_red_to_cost < s.relative_cost_tolerance or cost_red < s.absolute_cost_tolerance
-                       or ratios[1] < s.variables_tolerance)
-                rejected = new_cost > prev_cost or not ok_rate
-                if spec_pending and (rejected or rescaled):  # it assumed the full step stays applied
-                    e.spec_commit(False)
-                    spec_pending = False
-                if rejected:
-                    if last_troubled != it - 1:
-                        troubled_start_damping, troubled_start = damping, it
-                    damping *= s.damping_adjust_on_fail
-                    e.restore()
-                    if damping > s.damping_max:
-                        break
-                    last_troubled = it
-                else:
-                    if last_troubled == it - 1 and troubled_start_damping < 1e1 and damping > 1e-3:
-                        n_troubled += 1
-                        largest_troubled = max(largest_troubled, it - troubled_start)
-                    if ratio_red_to_exp >= s.min_relative_cost_reduction and applied > s.min_step_factor_for_good:
-                        damping = max(damping * s.damping_adjust_on_good_step, s.damping_min)
-                    else:
-                        damping *= s.damping_adjust_on_average_step
-                    final_cost = new_cost
-                self.reads_per_iteration.append((self.c.host_reads - reads0, rescaled))
-                reads0 = self.c.host_reads
-                it += 1
-                if not tol:
-                    last_impr = it
-                if it >= last_impr + s.stop_if_no_improvement_for and it >= last_troubled + s.distance_from_troubled_iteration:
-                    break
-                if it >= s.max_num_iterations:
-                    break
+            # the LM decisions (Optimizer.cpp:834-1097: csrc/lm_controller.hpp, the statement vb_optimize
+            # runs), identical on every rank; the engine's methods are looked up at each call
+            return lm_run(s, iteration=iteration, gradient_dot_step=gradient_dot_step,
+                          scale_step=lambda f: e.scale_step(f), restore=lambda: e.restore(),
+                          apply_step=lambda which: self.apply_step(which), cost=cost,
+                          solve_with_new_gradient=lambda: self.solve_with_new_gradient(),
+                          step_outcome=step_outcome, iteration_done=iteration_done)
         finally:
             if spec_pending:  # a convergence stop left it queued: never used
                 e.spec_commit(False)
             if deferred:
                 e.set_deferred(False)
             self.phases.close_iteration(final=True)
-        out = Summary()
-        out.initial_cost, out.final_cost = initial_cost, final_cost
-        out.num_troubled_seqs, out.largest_troubled_seq, out.num_iterations = n_troubled, largest_troubled, it
-        out.num_rescaled = n_rescaled
-        return out
 
 
 class _PhaseClock:

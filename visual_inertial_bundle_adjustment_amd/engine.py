@@ -75,6 +75,32 @@ LOG_CB = C.CFUNCTYPE(None, C.c_char_p, P)
 PRESTEP_CB = C.CFUNCTYPE(None, C.c_int, P)
 
 
+class CostStats(C.Structure):
+    """vb_cost_stats: CostStats (Factor.h:20-30)."""
+    _fields_ = [("num_total", C.c_int64), ("num_invalid", C.c_int64), ("num_prev_invalid", C.c_int64)]
+
+
+class LmIteration(C.Structure):
+    """vb_lm_iteration: what one iteration leaves for the LM decisions (vb_lm_run)."""
+    _fields_ = [("prev_cost", C.c_double), ("new_cost", C.c_double), ("model_reduction", C.c_double),
+                ("step_rms_ratio", C.c_double), ("stats", CostStats)]
+
+
+class LmOps(C.Structure):
+    """vb_lm_ops: the primitives vb_lm_run calls (user pointer first; the last two may be NULL)."""
+    _fields_ = [
+        ("iteration", C.CFUNCTYPE(C.c_int, P, C.c_int, C.c_double, C.c_int, C.POINTER(LmIteration))),
+        ("gradient_dot_step", C.CFUNCTYPE(C.c_int, P, C.c_int, _dp)),
+        ("scale_step", C.CFUNCTYPE(C.c_int, P, C.c_double)),
+        ("restore", C.CFUNCTYPE(C.c_int, P)),
+        ("apply_step", C.CFUNCTYPE(C.c_int, P, C.c_int)),
+        ("cost", C.CFUNCTYPE(C.c_int, P, _dp, C.POINTER(CostStats))),
+        ("solve_with_new_gradient", C.CFUNCTYPE(C.c_int, P)),
+        ("step_outcome", C.CFUNCTYPE(C.c_int, P, C.c_int, C.c_int)),
+        ("iteration_done", C.CFUNCTYPE(C.c_int, P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int)),
+    ]
+
+
 def _arr(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
