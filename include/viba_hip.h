@@ -32,6 +32,9 @@
  *   Optimizer::applyStep (Optimizer.cpp:121-134)               vb_apply_step
  *   backupVariables / restoreVariables (Optimizer.cpp:99-119)  vb_backup / vb_restore
  *   Optimizer::optimize (Optimizer.cpp:768-1106)               vb_optimize
+ *   SingleSessionAdapter::compareCalibrationVsFactory, the     vb_calib_projection_offsets
+ *     projection offsets (viba/single_session/
+ *     EvalCalibration.cpp:57-116)
  *
  * Conventions
  *   - All values are IEEE fp64 (the reference path is fp64 end to end).
@@ -614,6 +617,40 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
                        int64_t* n_failing);
 /* device time [ms] of the last vb_error_histogram's kernels (measurement aid) */
 int vb_report_device_ms(vb_handle h, double* ms);
+
+/* ---------------------------------------------------------------- calibration against factory
+ * The image projection offsets of SingleSessionAdapter::compareCalibrationVsFactory
+ * (viba/single_session/EvalCalibration.cpp:57-116, run by ark_vi_ba's --eval-calib-vs-factory,
+ * interfaces/ark/main_AriaKit_ViBa.cpp:116-120), evaluated on the device from the variables the handle holds.
+ * Factory camera c (factory_cam: VB_CAM_DATA doubles, factory_T_cam_bodyimu: 7) is walked on the grid
+ * x = fmod(w / 2, 20), + 20, ... < w, y = fmod(h / 2, 15), + 15, ... < h (w, h the record's image size; pixel
+ * index g = ix * ny + iy, the reference's loop order; max_grid = the largest nx * ny of the factory cameras).  A
+ * pixel is valid when, for its four corners px + (+-3, +-3), the factory model projects the unprojected corner
+ * (z >= 1e-6) back to within 1e-6 squared pixels; its ray is unproject(px).normalized(), factory model.
+ * Pair p = (cam_intr_var[p], cam_extr_var[p]) of VB_VAR_CAM_INTR / VB_VAR_CAM_EXTR handles, seen through factory
+ * camera fcam_of_pair[p]: for every valid pixel and distance d,
+ *   pc = T_var * (T_factory^-1 * (ray * d)),  value = |px - project_var(pc)|,  absent when pc.z < 1e-6.
+ * Pair p stands for weight[p] (rig, camera) entries of rigCamToModelIndex that share its two variables and adds
+ * its samples weight[p] times to series series_of_pair[p] (the reference's label: one slam camera).  Per
+ * (series, distance), row-major n_series x n_dist: count (samples, with weights), mean, rmse, and p50 / p90 as
+ * StatsValueContainer::pX (viba/common/StatsValueContainer.cpp:52-71: pos = pct / 100 * (N - 1), the sorted
+ * values at floor(pos) and ceil(pos) interpolated linearly).  The two ranks are found exactly, by a radix select
+ * over the values' bit patterns with 64-bit integer counts; the sums are reduced in a fixed order, so two calls
+ * return the same bits.  A series without samples gets count 0 and NaN statistics.
+ * Optional outputs (NULL to skip): values n_pairs x n_dist x max_grid (NaN = absent, invalid pixel or padding),
+ * valid n_fcam x max_grid.
+ * After vb_finalize (VB_E_STATE); VB_E_UNSUPPORTED on a landmark shard or a partitioned rank; VB_E_ARG for a
+ * variable, factory camera or series index out of range, a negative weight, n_dist <= 0, n_series <= 0, a
+ * non-finite distance, a factory record with an unknown model or an image size outside [1, 32767].  Reads the
+ * variables; the cost cache, the scalar slots, the step and the speculative buffers stay as they are. */
+int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* factory_cam,
+                                const double* factory_T_cam_bodyimu, int64_t n_pairs, const int32_t* cam_intr_var,
+                                const int32_t* cam_extr_var, const int32_t* fcam_of_pair, const int64_t* weight,
+                                const int32_t* series_of_pair, int32_t n_series, int32_t n_dist,
+                                const double* distances, int64_t* count, double* mean, double* rmse, double* p50,
+                                double* p90, double* values, uint8_t* valid);
+/* device time [ms] of the last vb_calib_projection_offsets' kernels (measurement aid) */
+int vb_calib_eval_device_ms(vb_handle h, double* ms);
 
 /* the HIP stream of the handle (hipStream_t), for interop with torch / RCCL */
 void* vb_stream(vb_handle h);

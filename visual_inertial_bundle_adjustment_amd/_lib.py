@@ -70,6 +70,9 @@ def load_host_lib() -> C.CDLL:
         lib.vbh_triangulate.restype = C.c_int
         lib.vbh_project.argtypes = [P, P, P]
         lib.vbh_unproject.argtypes = [P, P, P]
+        lib.vbh_calib_projection_offsets.argtypes = [C.c_int64, P, C.c_int64, P, C.c_int32, P, P, C.c_int64, P, P, P, P,
+                                                     P, C.c_int32, C.c_int32] + [P] * 8
+        lib.vbh_calib_projection_offsets.restype = C.c_int
         _host = lib
     return _host
 

@@ -81,6 +81,7 @@ class InitSettings:
     imu_extr_factory_calib_inflate: float = 100.0
     cam_extr_factory_calib_inflate: float = 100.0
     recompute_preint: bool = False
+    eval_calib_vs_factory: bool = False              # --eval-calib-vs-factory (calib_eval.py)
 
 
 class ImuJacIndices:
@@ -651,7 +652,8 @@ def save_outputs(out_dir: str, engine, p: SessionProblem, sd: SessionData):
 
 def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, settings: InitSettings | None = None,
                 optimizer_settings=None, refine: bool = True, log=print, show_histogram: bool = False,
-                simple_stats: bool = False, triangulate=None):
+                simple_stats: bool = False, triangulate=None, eval_calib_vs_factory: bool | None = None,
+                optimize: bool = True):
     """ark_vi_ba (interfaces/ark/main_AriaKit_ViBa.cpp:32-133) on a session folder: load, build indices,
     build the problem, rolling-shutter tables, refinePoints, Optimizer::optimize (with the per-iteration
     rolling-shutter rebuild and, under settings.recompute_preint, the preintegration recompute of the
@@ -659,7 +661,11 @@ def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, se
     engine).  show_histogram: log the residual report (report.residual_report: problem.showHistogram,
     main_AriaKit_ViBa.cpp:72,113) after refinePoints and after optimize, when the engine has the report
     calls.  triangulate: the triangulatePoint provider of the adapter (None: the host library;
-    engine.triangulate: the device).  Returns (engine, problem, summary)."""
+    engine.triangulate: the device).  eval_calib_vs_factory (None: settings.eval_calib_vs_factory): after the
+    final histogram and before the outputs, log the estimated calibration against the factory one
+    (calib_eval.compare_calibration_vs_factory, main_AriaKit_ViBa.cpp:116-120); it also runs with
+    optimize=False (--dont-optimize, :74), which skips Optimizer::optimize and its histogram and returns None
+    as the summary.  Returns (engine, problem, summary)."""
     from .engine import HipEngine, Settings
     s = settings or InitSettings()
     sd = SessionData.load(in_dir, load_imu=True)
@@ -682,10 +688,17 @@ def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, se
             log(residual_report(e, simple_stats=simple_stats).format())
 
     histogram()
-    summary = e.optimize(optimizer_settings or Settings.default())
-    if log:
-        log(f"[ark] optimize: {summary.initial_cost:.6g} -> {summary.final_cost:.6g} in {summary.num_iterations} iterations")
-    histogram()
+    summary = None
+    if optimize:
+        summary = e.optimize(optimizer_settings or Settings.default())
+        if log:
+            log(f"[ark] optimize: {summary.initial_cost:.6g} -> {summary.final_cost:.6g} in {summary.num_iterations} iterations")
+        histogram()
+    if s.eval_calib_vs_factory if eval_calib_vs_factory is None else eval_calib_vs_factory:
+        from .calib_eval import compare_calibration_vs_factory, show_calibration_comp_results
+        text = show_calibration_comp_results(compare_calibration_vs_factory(e, p, sd, m))
+        if log:
+            log(text)
     if out_dir:
         save_outputs(out_dir, e, p, sd)
     return e, p, summary

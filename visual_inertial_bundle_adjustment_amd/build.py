@@ -4,7 +4,8 @@
     lib/libviba_hip_mixed.so  the same with -DVIBA_MIXED=1 (config E: fp32 Jacobian records / Schur
                           products, fp64 Cholesky; csrc/engine.hpp)
     lib/libviba_synth.so  synthetic problem generator (g++)
-    lib/libviba_host.so   host side of the session adapter: initial point triangulation (g++)
+    lib/libviba_host.so   host side of the session adapter: initial point triangulation, the projection
+                          offsets of the calibration evaluation (g++)
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("VIBA_LIB_DIR", os.path.join(HERE, "lib"))
 HIP_SOURCES = ["factors.hip", "schur.hip", "solver.hip", "rs.hip", "preint.hip", "pcg.hip", "selinv.hip", "lowprec.hip", "api.hip",
                "optimize.hip", "symbolic.hip", "finalize.hip", "covariances.hip", "pointcov.hip", "report.hip", "multi.hip", "tools.hip",
-               "triangulate.hip"]
+               "triangulate.hip", "calib_eval.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("VIBA_OFFLOAD_ARCH", "gfx950")
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",

@@ -222,6 +222,7 @@ struct vb_handle_s {
   // obCostOrder, and the report's device state, made at its first call
   std::vector<int32_t> visRowOfPos;
   ReportState* rep = nullptr;
+  double calibEvalMs = 0.0;  // device time of the last vb_calib_projection_offsets' kernels (calib_eval.hip)
   bool finalized = false;
   Dev d;
   // symbolic (host)

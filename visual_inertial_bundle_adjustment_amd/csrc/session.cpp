@@ -2,12 +2,15 @@
 // triangulation of initPointsFromObservations (InitPointTracks.cpp:29-63 -> Triangulation.cpp:34-239).
 // It runs once before the LM loop, on the host as in the reference: a RANSAC over pairs of rays with the
 // reference's own random sequence (std::mt19937 seeded with pointId + 1729, std::uniform_int_distribution),
-// then two robust Gauss-Newton refinements.  Built into libviba_host.so (build.py), called by
+// then two robust Gauss-Newton refinements; and the host form of the calibration evaluation's projection
+// offsets (vbh_calib_projection_offsets, EvalCalibration.cpp:57-116).  Built into libviba_host.so (build.py), called by
 // visual_inertial_bundle_adjustment_amd/adapter.py through the C-ABI below.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
 #include <random>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -312,6 +315,133 @@ int vbh_project(const double* cam, const double* pc, double* uv) {
 int vbh_unproject(const double* cam, const double* uv, double* ray) {
   const V3 r = unproject(cam, uv);
   ray[0] = r.x, ray[1] = r.y, ray[2] = r.z;
+  return 0;
+}
+
+// The image projection offsets of SingleSessionAdapter::compareCalibrationVsFactory
+// (viba/single_session/EvalCalibration.cpp:57-116), the host form of vb_calib_projection_offsets
+// (include/viba_hip.h) with the camera variables as plain arrays (cam_intr: n_intr x 24, cam_extr: n_extr x 7)
+// instead of a handle.  Written the reference's way: every listed pair walks its grid, box check included, the
+// values are collected per (series, distance), sorted, and StatsValueContainer::pX reads the two ranks; a pair's
+// weight is the number of times each of its samples stands in the sorted sequence.  Returns 0, or -1 for the
+// arguments vb_calib_projection_offsets refuses with VB_E_ARG.
+int vbh_calib_projection_offsets(int64_t n_intr, const double* cam_intr, int64_t n_extr, const double* cam_extr,
+                                 int32_t n_fcam, const double* factory_cam, const double* factory_T_cam_bodyimu,
+                                 int64_t n_pairs, const int32_t* cam_intr_var, const int32_t* cam_extr_var,
+                                 const int32_t* fcam_of_pair, const int64_t* weight, const int32_t* series_of_pair,
+                                 int32_t n_series, int32_t n_dist, const double* distances, int64_t* count,
+                                 double* mean, double* rmse, double* p50, double* p90, double* values,
+                                 uint8_t* valid) {
+  constexpr double stepX = 20.0, stepY = 15.0;
+  if (n_dist <= 0 || !distances || n_series <= 0 || n_fcam < 0 || n_pairs < 0 || n_intr < 0 || n_extr < 0) return -1;
+  for (int32_t i = 0; i < n_dist; i++)
+    if (!std::isfinite(distances[i])) return -1;
+  int32_t maxGrid = 0;
+  for (int32_t c = 0; c < n_fcam; c++) {
+    const double* cam = factory_cam + 24 * (size_t)c;
+    if (cam[0] != 0.0 && cam[0] != 1.0) return -1;
+    const double w = cam[2], h = cam[3];
+    if (!(w >= 1 && w <= 32767 && h >= 1 && h <= 32767)) return -1;
+    int32_t nx = 0, ny = 0;
+    for (double x = std::fmod(w * 0.5, stepX); x < w; x += stepX) nx++;
+    for (double y = std::fmod(h * 0.5, stepY); y < h; y += stepY) ny++;
+    maxGrid = std::max(maxGrid, nx * ny);
+  }
+  for (int64_t p = 0; p < n_pairs; p++)
+    if (cam_intr_var[p] < 0 || cam_intr_var[p] >= n_intr || cam_extr_var[p] < 0 || cam_extr_var[p] >= n_extr ||
+        fcam_of_pair[p] < 0 || fcam_of_pair[p] >= n_fcam || weight[p] < 0 || series_of_pair[p] < 0 ||
+        series_of_pair[p] >= n_series)
+      return -1;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  if (values) std::fill(values, values + (size_t)n_pairs * n_dist * maxGrid, nan);
+  if (valid) std::fill(valid, valid + (size_t)n_fcam * maxGrid, (uint8_t)0);
+
+  // one grid walk (:73-110): fn(g, px, ray) for every pixel that passes the box check
+  auto walk = [&](const double* gtCam, auto&& fn) {
+    const double w = gtCam[2], h = gtCam[3];
+    int32_t ny = 0;
+    for (double y = std::fmod(h * 0.5, stepY); y < h; y += stepY) ny++;
+    int32_t ix = 0;
+    for (double x = std::fmod(w * 0.5, stepX); x < w; x += stepX, ix++) {
+      int32_t iy = 0;
+      for (double y = std::fmod(h * 0.5, stepY); y < h; y += stepY, iy++) {
+        bool bad = false;
+        for (int q = 0; q < 4; q++) {
+          const double ppx[2] = {x + ((q & 1) ? -3.0 : 3.0), y + ((q & 2) ? -3.0 : 3.0)};
+          const V3 ray = unproject(gtCam, ppx);
+          double ppx2[2], J[2][3];
+          const bool projOk = project(gtCam, ray, ppx2, J);
+          const double du = ppx[0] - ppx2[0], dv = ppx[1] - ppx2[1];
+          if (!projOk || du * du + dv * dv > 1e-6) {
+            bad = true;
+            break;
+          }
+        }
+        if (bad) continue;
+        const double px[2] = {x, y};
+        const V3 r = unproject(gtCam, px);
+        fn(ix * ny + iy, px, (1.0 / norm(r)) * r);
+      }
+    }
+  };
+
+  std::vector<std::vector<std::pair<double, int64_t>>> series((size_t)n_series * n_dist);
+  for (int64_t p = 0; p < n_pairs; p++) {
+    const int32_t fc = fcam_of_pair[p];
+    const double* gtCam = factory_cam + 24 * (size_t)fc;
+    const double* varCam = cam_intr + 24 * (size_t)cam_intr_var[p];
+    const Pose Tv(cam_extr + 7 * (size_t)cam_extr_var[p]), Tf(factory_T_cam_bodyimu + 7 * (size_t)fc);
+    const V3 tfi = Tf.rotT(-1.0 * Tf.t);  // T_factory^-1 = (R^T, -R^T t)
+    walk(gtCam, [&](int32_t g, const double* px, V3 ray) {
+      if (valid) valid[(size_t)fc * maxGrid + g] = 1;
+      for (int32_t d = 0; d < n_dist; d++) {
+        const V3 pc = Tv.act(Tf.rotT(distances[d] * ray) + tfi);
+        double px3[2], J[2][3];
+        if (!project(varCam, pc, px3, J)) continue;
+        const double du = px[0] - px3[0], dv = px[1] - px3[1];
+        const double e = std::sqrt(du * du + dv * dv);
+        if (values) values[((size_t)p * n_dist + d) * maxGrid + g] = e;
+        if (weight[p] > 0) series[(size_t)series_of_pair[p] * n_dist + d].push_back({e, weight[p]});
+      }
+    });
+  }
+  if (valid)  // the flags of the factory cameras no pair looks through
+    for (int32_t c = 0; c < n_fcam; c++) {
+      bool used = false;
+      for (int64_t p = 0; p < n_pairs && !used; p++) used = fcam_of_pair[p] == c;
+      if (!used) walk(factory_cam + 24 * (size_t)c, [&](int32_t g, const double*, V3) { valid[(size_t)c * maxGrid + g] = 1; });
+    }
+
+  for (size_t o = 0; o < series.size(); o++) {
+    auto& v = series[o];
+    int64_t N = 0;
+    double sum = 0.0, sq = 0.0;
+    for (const auto& [e, w] : v) N += w, sum += (double)w * e, sq += (double)w * e * e;
+    if (count) count[o] = N;
+    if (N == 0) {
+      if (mean) mean[o] = nan;
+      if (rmse) rmse[o] = nan;
+      if (p50) p50[o] = nan;
+      if (p90) p90[o] = nan;
+      continue;
+    }
+    if (mean) mean[o] = sum / (double)N;
+    if (rmse) rmse[o] = std::sqrt(sq / (double)N);
+    std::sort(v.begin(), v.end());
+    std::vector<int64_t> end(v.size());  // entry i stands at the sorted positions [end[i - 1], end[i])
+    int64_t cum = 0;
+    for (size_t i = 0; i < v.size(); i++) end[i] = cum += v[i].second;
+    auto at = [&](int64_t k) { return v[std::upper_bound(end.begin(), end.end(), k) - end.begin()].first; };
+    auto pX = [&](double percentile) {  // StatsValueContainer::pX (viba/common/StatsValueContainer.cpp:52-71)
+      const double pos = (percentile / 100.0) * (double)(N - 1);
+      const int64_t below = (int64_t)std::floor(pos), above = (int64_t)std::ceil(pos);
+      if (below == above) return at(below);
+      const double wAbove = pos - (double)below, wBelow = 1.0 - wAbove;
+      return at(below) * wBelow + at(above) * wAbove;
+    };
+    if (p50) p50[o] = pX(50.0);
+    if (p90) p90[o] = pX(90.0);
+  }
   return 0;
 }
 

@@ -661,6 +661,27 @@ class HipEngine(CEngineBase):
         self._check(self._fn("report_device_ms", [_dp])(self.h, C.byref(ms)))
         return ms.value
 
+    # ---------------------------------------------------------------- calibration against factory
+    def calib_projection_offsets(self, factory_cam, factory_T, cam_intr_var, cam_extr_var, fcam_of_pair, weight,
+                                 series_of_pair, n_series: int, distances, want_values: bool = False) -> dict:
+        """The image projection offsets of compareCalibrationVsFactory (EvalCalibration.cpp:57-116) on the
+        device (vb_calib_projection_offsets, include/viba_hip.h): pair p = the CAM_INTR / CAM_EXTR variables
+        (cam_intr_var[p], cam_extr_var[p]) seen through factory camera fcam_of_pair[p] (factory_cam (n, 24),
+        factory_T (n, 7)), standing for weight[p] (rig, camera) entries of series series_of_pair[p].  Returns
+        count, mean, rmse, p50, p90 of shape (n_series, len(distances)); with want_values also values
+        (n_pairs, len(distances), max_grid; NaN = absent) and valid (n_fcam, max_grid; bool)."""
+        from .calib_eval import offsets_call
+        f = self._fn("calib_projection_offsets", [C.c_int32, P, P, C.c_int64, P, P, P, P, P, C.c_int32, C.c_int32] +
+                     [P] * 8)
+        return offsets_call(lambda *a: self._check(f(self.h, *a)), factory_cam, factory_T, cam_intr_var, cam_extr_var,
+                            fcam_of_pair, weight, series_of_pair, n_series, distances, want_values)
+
+    def calib_eval_device_ms(self) -> float:
+        """device time [ms] of the last calib_projection_offsets' kernels (vb_calib_eval_device_ms)"""
+        ms = C.c_double()
+        self._check(self._fn("calib_eval_device_ms", [_dp])(self.h, C.byref(ms)))
+        return ms.value
+
     def profile_kernel(self, family: int):
         self._check(self._fn("profile_kernel", [C.c_int])(self.h, family))
 
