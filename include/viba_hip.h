@@ -396,6 +396,9 @@ int vb_debug_negate_model_reduction(vb_handle h, int iteration);
 int vb_debug_fail_iteration(vb_handle h, int iteration);
 /* test support: slot of reduced tile (I, J) in the vb_reduced_buffers tile store (-1: not stored) */
 int vb_debug_tile_slot(vb_handle h, int32_t I, int32_t J, int64_t* slot);
+/* test support: what this process holds from the HIP runtime through the library, over all handles and
+ * calls in flight: device bytes, pinned host bytes, events + streams.  Needs no handle and no device. */
+int vb_debug_live_resources(int64_t out[3]);
 /* iterations and relative residual of the last PCG solve (PCG::Result) */
 int vb_pcg_stats(vb_handle h, int32_t* iterations, double* relative_residual);
 /* step *= factor (in place) */

@@ -19,7 +19,7 @@ inline void profBegin(vb_handle h, int fam) {
   if (h->profUsed + 2 > h->profEv.size()) {
     for (int i = 0; i < 256; i++) {
       hipEvent_t e;
-      (void)hipEventCreate(&e);
+      (void)h->prof.event(&e);
       h->profEv.push_back(e);
     }
   }
@@ -370,23 +370,29 @@ int pcgPrepare(vb_handle h) {
   if (h->partSet || h->sharded)
     return fail(VB_E_UNSUPPORTED, "the PCG solvers run on a single handle (no landmark shards, no partition)");
   const int64_t nPad = (int64_t)d.nT * TS;
+  DevOwner& m = h->pcg;
+  bool ok = true;
   if (!h->symvTilesD) {
     std::vector<int32_t> tl, rc;
     for (int32_t J = 0; J < d.nT; J++)
       for (int64_t c = h->colStart[J]; c < h->colStart[J + 1]; c++)
         if (!h->tileFill[h->colTilesH[c]]) tl.push_back(h->colTilesH[c]), rc.push_back(h->colRowsH[c]), rc.push_back(J);
     h->nSymv = (int64_t)tl.size();
-    if (upload(&h->symvTilesD, tl) || upload(&h->symvRCD, rc) || alloc0(&h->pcgR, nPad) || alloc0(&h->pcgZ, nPad) ||
-        alloc0(&h->pcgP, nPad) || alloc0(&h->pcgAp, nPad) || alloc0(&h->pcgB, nPad))
-      return VB_E_HIP;
+    ok = !(m.put(&h->symvTilesD, tl) || m.put(&h->symvRCD, rc) || m.zeroed(&h->pcgR, nPad) || m.zeroed(&h->pcgZ, nPad) ||
+           m.zeroed(&h->pcgP, nPad) || m.zeroed(&h->pcgAp, nPad) || m.zeroed(&h->pcgB, nPad));
   }
-  if (h->solverType == VB_SOLVER_PCG_JACOBI && !h->jacL && alloc0(&h->jacL, nPad * 32)) return VB_E_HIP;
-  if (h->solverType == VB_SOLVER_PCG_GAUSS_SEIDEL && !h->tilesGS && alloc0(&h->tilesGS, d.nTiles * TS * TS))
-    return VB_E_HIP;
-  if (h->solverType == VB_SOLVER_PCG_LOWER_PREC && !h->lpTiles &&
-      (alloc0(&h->lpTiles, d.nTiles * TS * TS) || alloc0(&h->lpLinv, (size_t)d.nT * TS * TS) || alloc0(&h->lpT, nPad)))
-    return VB_E_HIP;
-  return 0;
+  if (ok && h->solverType == VB_SOLVER_PCG_JACOBI && !h->jacL) ok = !m.zeroed(&h->jacL, nPad * 32);
+  if (ok && h->solverType == VB_SOLVER_PCG_GAUSS_SEIDEL && !h->tilesGS) ok = !m.zeroed(&h->tilesGS, d.nTiles * TS * TS);
+  if (ok && h->solverType == VB_SOLVER_PCG_LOWER_PREC && !h->lpTiles)
+    ok = !(m.zeroed(&h->lpTiles, d.nTiles * TS * TS) || m.zeroed(&h->lpLinv, (size_t)d.nT * TS * TS) ||
+           m.zeroed(&h->lpT, nPad));
+  if (ok) return 0;
+  const int rc = devFail(m, "PCG buffers");
+  m.release();  // the whole group: the next call starts over
+  h->symvTilesD = h->symvRCD = nullptr;
+  h->pcgR = h->pcgZ = h->pcgP = h->pcgAp = h->pcgB = h->jacL = h->tilesGS = nullptr;
+  h->lpTiles = h->lpLinv = h->lpT = nullptr;
+  return rc;
 }
 
 // LowerPrecSolvePrecond::init (Preconditioner.h:180-218): S cast to fp32 and factored by the direct
@@ -575,7 +581,8 @@ int vb_create(const vb_config* cfg, vb_handle* out) {
   if (c.tile != 0 && c.tile != TS) return fail(VB_E_UNSUPPORTED, "only tile size 64 is built");
   if (c.device < 0 || c.device >= ndev) return fail(VB_E_ARG, "bad device ordinal");
   HIPCHK(hipSetDevice(c.device));
-  vb_handle h = new vb_handle_s();
+  std::unique_ptr<vb_handle_s> hp(new vb_handle_s());  // (a failure below gives back what was made so far)
+  vb_handle h = hp.get();
   h->cfg = c;
   if (const char* e = getenv("VIBA_SPEC_EARLY")) h->specEarly = e[0] != '0';
   if (const char* e = getenv("VIBA_COST_FUSE")) h->costFuse = e[0] != '0';
@@ -588,25 +595,16 @@ int vb_create(const vb_config* cfg, vb_handle* out) {
     if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0)
       h->numCUs = prop.multiProcessorCount;
   }
-  HIPCHK(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking));
-  for (auto& e : h->ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming));
-  HIPCHK(hipStreamCreateWithFlags(&h->stZ, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&h->evZero, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evSmallE, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evZJoin, hipEventDisableTiming));
-  HIPCHK(hipStreamCreateWithFlags(&h->stF, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&h->evSnFork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evClr, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evClrDone, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evInvDone, hipEventDisableTiming));
-  for (auto& e : h->evInvAt) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evStep, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->evRs, hipEventDisableTiming));
-  for (auto& e : h->evSnLvl) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  *out = h;
+  DevOwner& m = h->create;
+  bool bad = false;
+  for (hipStream_t* s : {&h->st, &h->st2, &h->stZ, &h->stF}) bad = bad || m.stream(s);
+  for (auto& e : h->ev) bad = bad || m.event(&e);
+  for (hipEvent_t* e : {&h->evFork, &h->evJoin, &h->evZero, &h->evSmallE, &h->evZJoin, &h->evSnFork, &h->evClr,
+                        &h->evClrDone, &h->evInvDone, &h->evStep, &h->evRs, &h->evInvAt[0], &h->evInvAt[1],
+                        &h->evInvAt[2], &h->evInvAt[3], &h->evSnLvl[0], &h->evSnLvl[1], &h->evSnLvl[2], &h->evSnLvl[3]})
+    bad = bad || m.event(e, hipEventDisableTiming);
+  if (bad) return devFail(m, "vb_create: stream / event");
+  *out = hp.release();
   return 0;
 }
 
@@ -614,78 +612,13 @@ int vb_destroy(vb_handle h) {
   if (!h) return 0;
   hipSetDevice(h->cfg.device);
   hipStreamSynchronize(h->st);
-  reportFree(h);
-  Dev& d = h->d;
-  void* ptrs[] = {d.rvKind, d.rvHandle, d.rvDim, d.rvOff, d.rvRowEnd, d.obCostOrder, d.obPack, d.obCP, d.obPose, d.obExtr, d.obIntr, d.obVel,
-                  d.obRS, d.obPt, d.obRed, d.obCol, d.obC, d.cache, d.Jt, d.lmObs, d.lmY, d.lmBlk, d.blkRed,
-                  d.blkCol, d.pcRow, d.pcBlk, d.bxStart, d.bxEnt, d.Vchol, d.gp, d.z, d.xp, d.Y, d.yZero, d.gpNew, d.zNew, d.ptLm, d.oxStart, d.oxObs, d.oxSlot,
-                  d.lxStart, d.lxLm, d.lxCol, d.lxChunk, d.tileWorks, d.schurRuns, d.schurTasks, d.tileEnts, d.grpStart, d.grpObs, d.grpRed, d.tileIdx, d.tiles, d.gRed, d.rhs, d.xRed, d.gRedNew, d.stepRed,
-                  d.stepPt, d.subRed, d.subPt, d.lmList, d.rsOff, d.rsS, d.rsI, d.rsG, d.rsN, d.imuT, d.imuV, d.rsMid, d.rsHalf,
-                  d.rsCalib, d.red, d.redS, d.err, h->colTilesD,
-                  h->colRowsD, h->rowTilesD, h->rowColD, h->padRowsD, h->colStartD, h->rowStartD, h->solveFlags, h->rootTilesD, h->rootRowsD, h->rootPack, h->rowPack, h->ownRowsD, h->ownPack, h->shardTilesD, h->shardPack, (void*)h->d.colOwner, h->dinv, h->yvec,
-                  h->rhsWork, h->linv, h->lscr, h->lscrSn, h->refStartD, h->refObsD, h->refPtD, h->refBackD, h->refAccD,
-                  h->symvTilesD, h->symvRCD, h->pcgR, h->pcgZ, h->pcgP, h->pcgAp, h->pcgB, h->jacL, h->tilesGS, h->lpTiles, h->lpLinv, h->lpT, h->clearTilesD,
-                  (void*)h->pi.src, (void*)h->pi.t, (void*)h->pi.v, (void*)h->pi.off, (void*)h->pi.noise,
-                  h->tilesAlt, h->cacheAlt, h->gRedAlt, h->rsSAlt, h->rsIAlt, h->rsGAlt, h->rsNAlt};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  for (int k = 0; k < 9; k++) {
-    if (d.var[k]) hipFree(d.var[k]);
-    if (d.varBak[k]) hipFree(d.varBak[k]);
-    if (d.redOf[k]) hipFree(d.redOf[k]);
-  }
-  for (int k = 0; k < 14; k++) {
-    if (d.sf[k].vars) hipFree(d.sf[k].vars);
-    if (d.sf[k].consts) hipFree(d.sf[k].consts);
-  }
-  {
-    if (d.sJ) hipFree(d.sJ);
-    if (d.sE) hipFree(d.sE);
-    if (d.sMeta) hipFree(d.sMeta);
-  }
-  for (auto& e : h->ev) hipEventDestroy(e);
-  if (h->evFork) hipEventDestroy(h->evFork);
-  if (h->evJoin) hipEventDestroy(h->evJoin);
-  if (h->st2) hipStreamSynchronize(h->st2), hipStreamDestroy(h->st2);
-  if (h->evZero) hipEventDestroy(h->evZero);
-  if (h->evSmallE) hipEventDestroy(h->evSmallE);
-  if (h->evZJoin) hipEventDestroy(h->evZJoin);
-  if (h->stZ) hipStreamSynchronize(h->stZ), hipStreamDestroy(h->stZ);
-  if (h->stF) hipStreamSynchronize(h->stF), hipStreamDestroy(h->stF);
-  if (h->evSnFork) hipEventDestroy(h->evSnFork);
-  if (h->evClr) hipEventDestroy(h->evClr);
-  if (h->evClrDone) hipEventDestroy(h->evClrDone);
-  if (h->evInvDone) hipEventDestroy(h->evInvDone);
-  for (auto& e : h->evInvAt)
-    if (e) hipEventDestroy(e);
-  if (h->evStep) hipEventDestroy(h->evStep);
-  if (h->evRs) hipEventDestroy(h->evRs);
-  for (hipEvent_t e : h->evSnLvl)
-    if (e) hipEventDestroy(e);
-  for (auto& e : h->profEv) hipEventDestroy(e);
-  if (h->evCost) hipEventDestroy(h->evCost);
-  for (auto& row : h->evS)
-    for (hipEvent_t e : row)
-      if (e) hipEventDestroy(e);
-  if (h->stR) hipStreamSynchronize(h->stR), hipStreamDestroy(h->stR);
-  if (h->hostRed) hipHostFree(h->hostRed);
-  for (SnSched& N : h->sn) {
-    for (void* p : {(void*)N.updD, (void*)N.fanPairsD, (void*)N.potD, (void*)N.rowD, (void*)N.fusD, (void*)N.copyD,
-                    (void*)N.invEarlyD, (void*)N.invLateD})
-      if (p) hipFree(p);
+  for (SnSched& N : h->sn)
     for (hipGraphExec_t g : N.graph)
       if (g) hipGraphExecDestroy(g);
-  }
-  for (Sched& S : h->sch) {
-    void* sp[] = {S.ptfD, S.ptfDiagD, S.potrfTileD, S.potrfColD, S.trsmDiagD, S.trsmTargetD, S.trsmColD, S.trsmRowD, S.updD, S.fanPairsD,
-                  S.tasksFD, S.tasksBD, S.expFD, S.expBD, S.preReadyD};
-    for (void* p : sp)
-      if (p) hipFree(p);
+  for (Sched& S : h->sch)
     for (hipGraphExec_t g : S.graph)
       if (g) hipGraphExecDestroy(g);
-  }
-  hipStreamDestroy(h->st);
-  delete h;
+  delete h;  // its owners (vb_handle_s) give back every buffer, event and stream
   return 0;
 }
 
@@ -866,7 +799,7 @@ int vb_get_factor_consts(vb_handle h, int kind, int64_t row, double* out) {
 int vb_refine_points(vb_handle h, double* costs, int64_t* stats) {
   if (!h || !h->finalized) return fail(VB_E_STATE, "vb_refine_points before vb_finalize");
   Dev& d = h->d;
-  if (h->partSet || d.lmB != 0 || d.lmE != d.nPts || !h->isRoot)
+  if (!wholeProblem(h, false))
     return fail(VB_E_UNSUPPORTED, "vb_refine_points needs the whole problem on this handle (no shard / partition)");
   if (!h->refStartD) {
     // observations grouped by point variable (refinePoints' perPointTracks, PointRefinement.cpp:20-45),
@@ -885,9 +818,14 @@ int vb_refine_points(vb_handle h, double* costs, int64_t* stats) {
     for (int64_t p = 0; p < nP; p++)
       if (cnt[p + 1] > cnt[p]) gp.push_back((int32_t)p), gs.push_back(cnt[p + 1]);
     h->nRefG = (int64_t)gp.size();
-    if (upload(&h->refStartD, gs) || upload(&h->refObsD, obs) || upload(&h->refPtD, gp) ||
-        alloc0(&h->refBackD, (size_t)d.nObs) || alloc0(&h->refAccD, 8))
-      return VB_E_HIP;
+    DevOwner& m = h->refine;
+    if (m.put(&h->refStartD, gs) || m.put(&h->refObsD, obs) || m.put(&h->refPtD, gp) ||
+        m.zeroed(&h->refBackD, (size_t)d.nObs) || m.zeroed(&h->refAccD, 8)) {
+      const int rc = devFail(m, "vb_refine_points: device allocation");
+      m.release();  // the next call starts over
+      h->refStartD = nullptr, h->refObsD = h->refPtD = nullptr, h->refBackD = h->refAccD = nullptr;
+      return rc;
+    }
   }
   HIPCHK(hipMemsetAsync(h->refAccD, 0, 8 * sizeof(double), h->st));
   HIPCHK(hipMemsetAsync(d.err, 0, 2 * sizeof(int32_t), h->st));
@@ -1166,6 +1104,11 @@ int vb_debug_fail_iteration(vb_handle h, int iteration) {
   return 0;
 }
 // slot of tile (I, J) of the reduced tile store (vb_reduced_buffers), -1 when it is not stored
+int vb_debug_live_resources(int64_t out[3]) {
+  if (!out) return fail(VB_E_ARG, "vb_debug_live_resources: null argument");
+  for (int i = 0; i < 3; i++) out[i] = g_live[i].load();
+  return 0;
+}
 int vb_debug_tile_slot(vb_handle h, int32_t I, int32_t J, int64_t* slot) {
   if (!h || !h->finalized || !slot) return fail(VB_E_STATE, "vb_debug_tile_slot before vb_finalize");
   *slot = -1;

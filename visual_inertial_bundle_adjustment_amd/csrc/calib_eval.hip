@@ -281,45 +281,6 @@ __global__ void __launch_bounds__(64) ce_quantile_kernel(CeArgs A) {
 }  // namespace
 }  // namespace viba
 
-namespace viba_host {
-namespace {
-
-// frees its device buffers and events when the call returns, on every path
-struct CeScratch {
-  std::vector<void*> p;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~CeScratch() {
-    for (void* q : p) hipFree(q);
-    for (hipEvent_t e : ev)
-      if (e) hipEventDestroy(e);
-  }
-  template <typename T>
-  int get(T** out, size_t n) {
-    void* q = nullptr;
-    HIPCHK(hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T)));
-    p.push_back(q);
-    *out = (T*)q;
-    return 0;
-  }
-  template <typename T>
-  int put(const T** out, const T* src, size_t n, hipStream_t st) {
-    T* q = nullptr;
-    if (int rc = get(&q, n)) return rc;
-    if (n) HIPCHK(hipMemcpyAsync(q, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-    *out = q;
-    return 0;
-  }
-};
-
-template <typename T>
-int ceDownload(T* host, const T* dev, size_t n, hipStream_t st) {
-  if (host && n) HIPCHK(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
-  return 0;
-}
-
-}  // namespace
-}  // namespace viba_host
-
 extern "C" {
 
 int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* factory_cam,
@@ -332,7 +293,7 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
   if (!h) return fail(VB_E_ARG, std::string(what) + ": null handle");
   if (!h->finalized) return fail(VB_E_STATE, std::string(what) + " before vb_finalize");
   const Dev& d = h->d;
-  if (h->partSet || h->sharded || d.lmB != 0 || d.lmE != d.nPts || !h->isRoot)
+  if (!wholeProblem(h))
     return fail(VB_E_UNSUPPORTED, std::string(what) + " needs the whole problem on this handle (no shard / partition)");
   if (n_dist <= 0 || !distances) return fail(VB_E_ARG, std::string(what) + ": n_dist must be positive");
   if (n_series <= 0 || n_fcam < 0 || n_pairs < 0) return fail(VB_E_ARG, std::string(what) + ": bad count");
@@ -388,7 +349,8 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
   if (nBlk * n_dist >= ((int64_t)1 << 31)) return fail(VB_E_ARG, std::string(what) + ": too many pairs for one call");
   HIPCHK(hipSetDevice(h->cfg.device));
   hipStream_t st = h->st;
-  CeScratch S;
+  DevOwner S;  // frees its buffers and events when the call returns, on every path
+  hipEvent_t ev[2] = {nullptr, nullptr};
   const size_t nFG = (size_t)n_fcam * maxGrid, nVal = (size_t)n_pairs * n_dist * maxGrid;
   if (S.put(&A.grid, grid.data(), grid.size(), st) || S.put(&A.fcam, factory_cam, (size_t)n_fcam * VB_CAM_DATA, st) ||
       S.put(&A.fT, factory_T_cam_bodyimu, (size_t)n_fcam * 7, st) || S.put(&A.dist, distances, n_dist, st) ||
@@ -398,13 +360,11 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
       S.get(&A.values, nVal) || S.get(&A.slabN, (size_t)nBlk * n_dist) || S.get(&A.slabS, (size_t)nBlk * n_dist) ||
       S.get(&A.slabQ, (size_t)nBlk * n_dist) || S.get(&A.count, nSD) || S.get(&A.mean, nSD) || S.get(&A.rmse, nSD) ||
       S.get(&A.p50, nSD) || S.get(&A.p90, nSD) || S.get(&A.rankLeft, kCeRanks * nSD) ||
-      S.get(&A.prefix, kCeRanks * nSD) || S.get(&A.bins, kCeRanks * nSD * 256))
-    return VB_E_HIP;
+      S.get(&A.prefix, kCeRanks * nSD) || S.get(&A.bins, kCeRanks * nSD * 256) || S.event(&ev[0]) || S.event(&ev[1]))
+    return devFail(S, std::string(what) + ": device allocation");
   A.varIntr = d.var[VB_VAR_CAM_INTR], A.varExtr = d.var[VB_VAR_CAM_EXTR];
-  HIPCHK(hipEventCreate(&S.ev[0]));
-  HIPCHK(hipEventCreate(&S.ev[1]));
   HIPCHK(hipMemsetAsync(A.bins, 0, kCeRanks * nSD * 256 * sizeof(unsigned long long), st));
-  HIPCHK(hipEventRecord(S.ev[0], st));
+  HIPCHK(hipEventRecord(ev[0], st));
   hipLaunchKernelGGL(ce_grid_kernel, dim3((unsigned)((nFG + kCeBlock - 1) / kCeBlock)), dim3(kCeBlock), 0, st, A);
   hipLaunchKernelGGL(ce_offset_kernel, dim3((unsigned)nBlk), dim3(kCeBlock), 0, st, A);
   hipLaunchKernelGGL(ce_stats_kernel, dim3((unsigned)nSD), dim3(kCeBlock), 0, st, A);
@@ -414,14 +374,14 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
   }
   hipLaunchKernelGGL(ce_quantile_kernel, dim3((unsigned)((nSD + 63) / 64)), dim3(64), 0, st, A);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(S.ev[1], st));
-  if (ceDownload(count, A.count, nSD, st) || ceDownload(mean, A.mean, nSD, st) || ceDownload(rmse, A.rmse, nSD, st) ||
-      ceDownload(p50, A.p50, nSD, st) || ceDownload(p90, A.p90, nSD, st) || ceDownload(values, A.values, nVal, st) ||
-      ceDownload(valid, A.valid, nFG, st))
+  HIPCHK(hipEventRecord(ev[1], st));
+  if (download(count, A.count, nSD, st) || download(mean, A.mean, nSD, st) || download(rmse, A.rmse, nSD, st) ||
+      download(p50, A.p50, nSD, st) || download(p90, A.p90, nSD, st) || download(values, A.values, nVal, st) ||
+      download(valid, A.valid, nFG, st))
     return VB_E_HIP;
   HIPCHK(hipStreamSynchronize(st));
   float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+  HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
   h->calibEvalMs = ms;
   return 0;
 }

@@ -72,22 +72,17 @@ int selectedInversion(vb_handle h) {
     maxU = std::max<int64_t>(maxU, u);
     lvU[k + 1] = (int64_t)uIt.size() / 2, lvZ[k + 1] = (int64_t)zIt.size() / 4, lvD[k + 1] = (int64_t)dIt.size() / 2;
   }
+  DevOwner m;  // the level lists and the U scratch, freed when the call returns
   int32_t *uD = nullptr, *zD = nullptr, *dD = nullptr;
   double* U = nullptr;
-  int rc = 0;
-  if (upload(&uD, uIt) || upload(&zD, zIt) || upload(&dD, dIt) ||
-      hipMalloc((void**)&U, (size_t)maxU * TS * TS * sizeof(double)) != hipSuccess) {
-    rc = fail(VB_E_HIP, "selected inversion: device allocation");
-  } else {
-    for (int32_t k = 0; k < nLev; k++)
-      launch_selinv_level(d.tiles, d.tileIdx, nT, h->colStartD, h->colRowsD, h->colTilesD, h->linv, U,
-                          uD + 2 * lvU[k], (int)(lvU[k + 1] - lvU[k]), zD + 4 * lvZ[k], (int)(lvZ[k + 1] - lvZ[k]),
-                          dD + 2 * lvD[k], (int)(lvD[k + 1] - lvD[k]), h->st);
-    if (hipStreamSynchronize(h->st) != hipSuccess) rc = fail(VB_E_HIP, "selected inversion: kernel failure");
-  }
-  for (void* p : {(void*)uD, (void*)zD, (void*)dD, (void*)U})
-    if (p) (void)hipFree(p);
-  return rc;
+  if (m.put(&uD, uIt) || m.put(&zD, zIt) || m.put(&dD, dIt) || m.get(&U, (size_t)maxU * TS * TS))
+    return fail(VB_E_HIP, "selected inversion: device allocation");
+  for (int32_t k = 0; k < nLev; k++)
+    launch_selinv_level(d.tiles, d.tileIdx, nT, h->colStartD, h->colRowsD, h->colTilesD, h->linv, U,
+                        uD + 2 * lvU[k], (int)(lvU[k + 1] - lvU[k]), zD + 4 * lvZ[k], (int)(lvZ[k + 1] - lvZ[k]),
+                        dD + 2 * lvD[k], (int)(lvD[k + 1] - lvD[k]), h->st);
+  if (hipStreamSynchronize(h->st) != hipSuccess) return fail(VB_E_HIP, "selected inversion: kernel failure");
+  return 0;
 }
 
 int vb_compute_covariances(vb_handle h, double damping, int64_t n_blocks, const int64_t* block_start,
@@ -176,21 +171,15 @@ int vb_compute_covariances(vb_handle h, double damping, int64_t n_blocks, const 
     for (int64_t q = 0; q < n_blocks; q++)  // solved blocks: gather anything (their slots are overwritten below)
       if (bySolve[q]) std::fill(gidx.begin() + outOff[q], gidx.begin() + outOff[q + 1], 0);
     const int64_t ng = (int64_t)gidx.size();
+    DevOwner m;  // freed at the end of the block, on every path
     int64_t* idxD = nullptr;
     double* valD = nullptr;
     std::vector<double> val(ng);
-    int rc = 0;
-    if (upload(&idxD, gidx) || hipMalloc((void**)&valD, std::max<int64_t>(1, ng) * sizeof(double)) != hipSuccess) {
-      rc = fail(VB_E_HIP, "covariances: device allocation");
-    } else {
-      launch_gather(d.tiles, idxD, ng, valD, h->st);
-      if (hipMemcpyAsync(val.data(), valD, ng * sizeof(double), hipMemcpyDeviceToHost, h->st) != hipSuccess ||
-          hipStreamSynchronize(h->st) != hipSuccess)
-        rc = fail(VB_E_HIP, "covariances: gather");
-    }
-    if (idxD) (void)hipFree(idxD);
-    if (valD) (void)hipFree(valD);
-    if (rc) return rc;
+    if (m.put(&idxD, gidx) || m.get(&valD, ng)) return fail(VB_E_HIP, "covariances: device allocation");
+    launch_gather(d.tiles, idxD, ng, valD, h->st);
+    if (hipMemcpyAsync(val.data(), valD, ng * sizeof(double), hipMemcpyDeviceToHost, h->st) != hipSuccess ||
+        hipStreamSynchronize(h->st) != hipSuccess)
+      return fail(VB_E_HIP, "covariances: gather");
     for (int64_t q = 0; q < n_blocks; q++)
       if (!bySolve[q]) std::copy(val.begin() + outOff[q], val.begin() + outOff[q + 1], out + outOff[q]);
   }
@@ -269,22 +258,19 @@ int vb_compute_point_covariances(vb_handle h, double damping, int64_t n, const i
   if (d.nT > 0)
     if (int rc = selectedInversion(h)) return rc;
   const auto t2 = now();
-  int32_t *itemsD = nullptr, *reqLmD = nullptr, *xPcD = nullptr;
-  int64_t *xStartD = nullptr, *outOffD = nullptr;
-  double* outD = nullptr;
-  int rc = 0;
-  if (upload(&itemsD, items) || upload(&reqLmD, reqLm) || upload(&xPcD, xPc) || upload(&xStartD, xStart) ||
-      upload(&outOffD, outOff) || hipMalloc((void**)&outD, (size_t)outOff[n] * sizeof(double)) != hipSuccess) {
-    rc = fail(VB_E_HIP, "point covariances: device allocation");
-  } else {
+  {
+    DevOwner m;  // freed at the end of the block (inside the third time), on every path
+    int32_t *itemsD = nullptr, *reqLmD = nullptr, *xPcD = nullptr;
+    int64_t *xStartD = nullptr, *outOffD = nullptr;
+    double* outD = nullptr;
+    if (m.put(&itemsD, items) || m.put(&reqLmD, reqLm) || m.put(&xPcD, xPc) || m.put(&xStartD, xStart) ||
+        m.put(&outOffD, outOff) || m.get(&outD, (size_t)outOff[n]))
+      return fail(VB_E_HIP, "point covariances: device allocation");
     launch_pointcov(d, itemsD, nSmall, nBig, reqLmD, xStartD, xPcD, outOffD, outD, h->st);
     if (hipMemcpyAsync(out, outD, (size_t)outOff[n] * sizeof(double), hipMemcpyDeviceToHost, h->st) != hipSuccess ||
         hipStreamSynchronize(h->st) != hipSuccess)
-      rc = fail(VB_E_HIP, "point covariances: kernel failure");
+      return fail(VB_E_HIP, "point covariances: kernel failure");
   }
-  for (void* p : {(void*)itemsD, (void*)reqLmD, (void*)xPcD, (void*)xStartD, (void*)outOffD, (void*)outD})
-    if (p) (void)hipFree(p);
-  if (rc) return rc;
   const auto t3 = now();
   h->pointCovMs[0] = ms(t0, t1), h->pointCovMs[1] = ms(t1, t2), h->pointCovMs[2] = ms(t2, t3);
   return checkErr(h);

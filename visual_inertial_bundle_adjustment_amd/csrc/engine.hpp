@@ -177,7 +177,6 @@ struct Dev {
   rec_t* yZero = nullptr;  // 256 zeros: the gathers of K rows past a Schur task's landmarks
   rec_t* Y = nullptr;  // landmark panels Y = L^-1 W, plane-interleaved: row q of global panel column c at Y[3 c + q] (fp32 in the VIBA_MIXED build)
   double *gpNew = nullptr, *zNew = nullptr;
-  int32_t* ptRed = nullptr;  // point param registered? (1/0) per point var handle
   int32_t* ptLm = nullptr;   // point var handle -> landmark index (-1)
   // per reduced variable incidence lists
   int64_t* oxStart = nullptr;
@@ -207,7 +206,6 @@ struct Dev {
   int64_t nTiles = 0;
   int32_t* tileIdx = nullptr;  // nT * nT
   double* tiles = nullptr;
-  int64_t* colStart = nullptr;  // host-side copy used for launches
   // reduced vectors
   double *gRed = nullptr, *rhs = nullptr, *xRed = nullptr, *gRedNew = nullptr;
   double *stepRed = nullptr, *stepPt = nullptr, *subRed = nullptr, *subPt = nullptr;

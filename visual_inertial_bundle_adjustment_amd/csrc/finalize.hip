@@ -15,22 +15,22 @@ Knobs readKnobs(const vb_handle_s& h) {
   return k;
 }
 
-int uploadSched(const SchedHost& H, Sched& S) {
+int uploadSched(DevOwner& m, const SchedHost& H, Sched& S) {
   static_cast<SchedShape&>(S) = H;
-  if (upload(&S.potrfTileD, H.potrfTile) || upload(&S.potrfColD, H.potrfCol) || upload(&S.trsmDiagD, H.trsmDiag) ||
-      upload(&S.trsmTargetD, H.trsmTarget) || upload(&S.trsmColD, H.trsmCol) || upload(&S.trsmRowD, H.trsmRow) ||
-      upload(&S.updD, H.upd) || upload(&S.fanPairsD, H.fanPairs) || upload(&S.tasksFD, H.tasksF) ||
-      upload(&S.tasksBD, H.tasksB) || upload(&S.expFD, H.expF) || upload(&S.expBD, H.expB) ||
-      upload(&S.preReadyD, H.preReady) || upload(&S.ptfD, H.ptf) || upload(&S.ptfDiagD, H.ptfDiag))
+  if (m.put(&S.potrfTileD, H.potrfTile) || m.put(&S.potrfColD, H.potrfCol) || m.put(&S.trsmDiagD, H.trsmDiag) ||
+      m.put(&S.trsmTargetD, H.trsmTarget) || m.put(&S.trsmColD, H.trsmCol) || m.put(&S.trsmRowD, H.trsmRow) ||
+      m.put(&S.updD, H.upd) || m.put(&S.fanPairsD, H.fanPairs) || m.put(&S.tasksFD, H.tasksF) ||
+      m.put(&S.tasksBD, H.tasksB) || m.put(&S.expFD, H.expF) || m.put(&S.expBD, H.expB) ||
+      m.put(&S.preReadyD, H.preReady) || m.put(&S.ptfD, H.ptf) || m.put(&S.ptfDiagD, H.ptfDiag))
     return VB_E_HIP;
   return 0;
 }
 
-int uploadSnSched(const SnSchedHost& H, SnSched& S) {
+int uploadSnSched(DevOwner& m, const SnSchedHost& H, SnSched& S) {
   static_cast<SnSchedShape&>(S) = H;
-  if (upload(&S.updD, H.upd) || upload(&S.fanPairsD, H.fanPairs) || upload(&S.potD, H.pot) || upload(&S.rowD, H.row) ||
-      upload(&S.fusD, H.fus) || upload(&S.copyD, H.copy) || upload(&S.invEarlyD, H.invEarly) ||
-      upload(&S.invLateD, H.invLate))
+  if (m.put(&S.updD, H.upd) || m.put(&S.fanPairsD, H.fanPairs) || m.put(&S.potD, H.pot) || m.put(&S.rowD, H.row) ||
+      m.put(&S.fusD, H.fus) || m.put(&S.copyD, H.copy) || m.put(&S.invEarlyD, H.invEarly) ||
+      m.put(&S.invLateD, H.invLate))
     return VB_E_HIP;
   return 0;
 }
@@ -89,23 +89,17 @@ void copyToHandle(vb_handle h, const Symbolic& A) {
 // the rolling-shutter tables: rebuilt on the device (capacities from the IMU stream), or as given
 int uploadRsTables(vb_handle h) {
   Dev& d = h->d;
+  DevOwner& m = h->fin;
   if (h->rsDevice) {
-    // table capacity: the IMU samples of [mid - half, mid + half] widened by 20 ms on both sides (the
-    // reference-time offsets of the calibration move the gyro boundaries by far less), + 4
-    const int64_t kWidenNs = 20000000;
     h->rsOff.assign(h->nRS + 1, 0);
-    for (int32_t t = 0; t < h->nRS; t++) {
-      const int64_t a = (h->rsMid[t] - h->rsHalf[t]) * 1000 - kWidenNs, b = (h->rsMid[t] + h->rsHalf[t]) * 1000 + kWidenNs;
-      const int64_t cnt = std::upper_bound(h->imuT.begin(), h->imuT.end(), b) -
-                          std::lower_bound(h->imuT.begin(), h->imuT.end(), a);
-      h->rsOff[t + 1] = h->rsOff[t] + cnt + 4;
-    }
+    for (int32_t t = 0; t < h->nRS; t++)
+      h->rsOff[t + 1] = h->rsOff[t] + rsTableCapacity(h->imuT.data(), (int64_t)h->imuT.size(), h->rsMid[t], h->rsHalf[t]);
     const int64_t ns = h->rsOff[h->nRS];
     std::vector<int32_t> zeroN(h->nRS, 0);
-    if (upload(&d.rsOff, h->rsOff) || alloc0(&d.rsS, ns * 11) || alloc0(&d.rsI, (ns - h->nRS) * 9) ||
-        alloc0(&d.rsG, (size_t)h->nRS * 3) || upload(&d.rsN, zeroN) || upload(&d.imuT, h->imuT) ||
-        upload(&d.imuV, h->imuV) || upload(&d.rsMid, h->rsMid) || upload(&d.rsHalf, h->rsHalf) ||
-        upload(&d.rsCalib, h->rsCalib))
+    if (m.put(&d.rsOff, h->rsOff) || m.zeroed(&d.rsS, ns * 11) || m.zeroed(&d.rsI, (ns - h->nRS) * 9) ||
+        m.zeroed(&d.rsG, (size_t)h->nRS * 3) || m.put(&d.rsN, zeroN) || m.put(&d.imuT, h->imuT) ||
+        m.put(&d.imuV, h->imuV) || m.put(&d.rsMid, h->rsMid) || m.put(&d.rsHalf, h->rsHalf) ||
+        m.put(&d.rsCalib, h->rsCalib))
       return VB_E_HIP;
     d.nImu = (int64_t)h->imuT.size();
     d.rsGravVar = h->rsGravVar;
@@ -114,105 +108,119 @@ int uploadRsTables(vb_handle h) {
   std::vector<int32_t> cnt(h->nRS);
   for (int32_t t = 0; t < h->nRS; t++) cnt[t] = (int32_t)(h->rsOff[t + 1] - h->rsOff[t]);
   if (h->rsOff.empty()) h->rsOff.assign(1, 0);
-  if (upload(&d.rsOff, h->rsOff) || upload(&d.rsS, h->rsS) || upload(&d.rsI, h->rsI) || upload(&d.rsG, h->rsG) ||
-      upload(&d.rsN, cnt))
+  if (m.put(&d.rsOff, h->rsOff) || m.put(&d.rsS, h->rsS) || m.put(&d.rsI, h->rsI) || m.put(&d.rsG, h->rsG) ||
+      m.put(&d.rsN, cnt))
     return VB_E_HIP;
   return 0;
 }
 
-// every device buffer of vb_finalize.  Each pointer lands in the handle as it is made, so vb_destroy
-// frees what exists after a failure.
+// every device buffer of vb_finalize, owned by the handle's `fin` group
 int uploadAll(vb_handle h, const Symbolic& A) {
   Dev& d = h->d;
+  DevOwner& m = h->fin;
   const int64_t nPts = A.reg.nPts, nObs = A.obs.nObs, nTiles = A.pat.nTiles;
   const int32_t nT = A.lay.nT;
   // variables and the reduced layout
   for (int k = 0; k < 9; k++)
-    if (upload(&d.var[k], h->data[k]) || alloc0(&d.varBak[k], h->data[k].size()) || upload(&d.redOf[k], A.lay.redOf[k]))
+    if (m.put(&d.var[k], h->data[k]) || m.zeroed(&d.varBak[k], h->data[k].size()) || m.put(&d.redOf[k], A.lay.redOf[k]))
       return VB_E_HIP;
-  if (upload(&d.rvKind, A.lay.rvKind) || upload(&d.rvHandle, A.lay.rvHandle) || upload(&d.rvDim, A.lay.rvDim) ||
-      upload(&d.rvOff, A.lay.rvOff) || upload(&d.rvRowEnd, A.pat.rowEnd) || upload(&h->padRowsD, A.lay.padRows))
+  if (m.put(&d.rvKind, A.lay.rvKind) || m.put(&d.rvHandle, A.lay.rvHandle) || m.put(&d.rvDim, A.lay.rvDim) ||
+      m.put(&d.rvOff, A.lay.rvOff) || m.put(&d.rvRowEnd, A.pat.rowEnd) || m.put(&h->padRowsD, A.lay.padRows))
     return VB_E_HIP;
-  {
-    int8_t* co = nullptr;
-    if (upload(&co, A.lay.colOwner)) return VB_E_HIP;
-    d.colOwner = co;
-  }
+  if (m.put(&d.colOwner, A.lay.colOwner)) return VB_E_HIP;
   // observations
-  if (upload(&d.obCostOrder, A.cost.order) || upload(&d.obPack, A.cost.pack) || upload(&d.obCP, A.cost.cp) ||
-      upload(&d.obPose, A.obs.obPose) || upload(&d.obExtr, A.obs.obExtr) || upload(&d.obIntr, A.obs.obIntr) ||
-      upload(&d.obVel, A.obs.obVel) || upload(&d.obRS, A.obs.obRS) || upload(&d.obPt, A.obs.obPt) ||
-      upload(&d.obRed, A.obs.obRed) || upload(&d.obCol, A.pan.obCol) || upload(&d.obC, A.obs.obC) ||
-      alloc0(&d.cache, nObs) || alloc0(&d.Jt, (size_t)kJPlanes * d.nObsPad))
+  if (m.put(&d.obCostOrder, A.cost.order) || m.put(&d.obPack, A.cost.pack) || m.put(&d.obCP, A.cost.cp) ||
+      m.put(&d.obPose, A.obs.obPose) || m.put(&d.obExtr, A.obs.obExtr) || m.put(&d.obIntr, A.obs.obIntr) ||
+      m.put(&d.obVel, A.obs.obVel) || m.put(&d.obRS, A.obs.obRS) || m.put(&d.obPt, A.obs.obPt) ||
+      m.put(&d.obRed, A.obs.obRed) || m.put(&d.obCol, A.pan.obCol) || m.put(&d.obC, A.obs.obC) ||
+      m.zeroed(&d.cache, nObs) || m.zeroed(&d.Jt, (size_t)kJPlanes * d.nObsPad))
     return VB_E_HIP;
   d.cacheW = d.cache;
   // landmarks
-  if (upload(&d.lmList, A.shard.lmList) || upload(&d.lmObs, A.obs.lmObs) || upload(&d.lmY, A.pan.lmY) ||
-      upload(&d.lmBlk, A.pan.lmBlk) || upload(&d.blkRed, A.pan.blkRed) || upload(&d.blkCol, A.pan.blkCol) ||
-      upload(&d.ptLm, A.reg.lmOfPoint) || upload(&d.pcRow, A.pan.pcRow) || upload(&d.pcBlk, A.pan.pcBlk) ||
-      upload(&d.bxStart, A.pan.bxStart) || upload(&d.bxEnt, A.pan.bxEnt))
+  if (m.put(&d.lmList, A.shard.lmList) || m.put(&d.lmObs, A.obs.lmObs) || m.put(&d.lmY, A.pan.lmY) ||
+      m.put(&d.lmBlk, A.pan.lmBlk) || m.put(&d.blkRed, A.pan.blkRed) || m.put(&d.blkCol, A.pan.blkCol) ||
+      m.put(&d.ptLm, A.reg.lmOfPoint) || m.put(&d.pcRow, A.pan.pcRow) || m.put(&d.pcBlk, A.pan.pcBlk) ||
+      m.put(&d.bxStart, A.pan.bxStart) || m.put(&d.bxEnt, A.pan.bxEnt))
     return VB_E_HIP;
-  if (alloc0(&d.Vchol, nPts * 6) || alloc0(&d.gp, nPts * 3) || alloc0(&d.z, nPts * 3) || alloc0(&d.xp, nPts * 3) ||
-      alloc0(&d.Y, A.pan.lmY[nPts] + 128) || alloc0(&d.yZero, 256) ||  // + the over-read of the Schur gathers
-      alloc0(&d.gpNew, nPts * 3) || alloc0(&d.zNew, nPts * 3))
+  if (m.zeroed(&d.Vchol, nPts * 6) || m.zeroed(&d.gp, nPts * 3) || m.zeroed(&d.z, nPts * 3) || m.zeroed(&d.xp, nPts * 3) ||
+      m.zeroed(&d.Y, A.pan.lmY[nPts] + 128) || m.zeroed(&d.yZero, 256) ||  // + the over-read of the Schur gathers
+      m.zeroed(&d.gpNew, nPts * 3) || m.zeroed(&d.zNew, nPts * 3))
     return VB_E_HIP;
-  if (upload(&d.oxStart, A.pan.oxStart) || upload(&d.oxObs, A.pan.oxObs) || upload(&d.oxSlot, A.pan.oxSlot) ||
-      upload(&d.lxStart, A.pan.lxStart) || upload(&d.lxLm, A.pan.lxLm) || upload(&d.lxCol, A.pan.lxCol) ||
-      upload(&d.lxChunk, A.pan.lxChunk))
+  if (m.put(&d.oxStart, A.pan.oxStart) || m.put(&d.oxObs, A.pan.oxObs) || m.put(&d.oxSlot, A.pan.oxSlot) ||
+      m.put(&d.lxStart, A.pan.lxStart) || m.put(&d.lxLm, A.pan.lxLm) || m.put(&d.lxCol, A.pan.lxCol) ||
+      m.put(&d.lxChunk, A.pan.lxChunk))
     return VB_E_HIP;
   // Schur work
-  if (upload(&d.grpStart, A.schur.grpStart) || upload(&d.grpObs, A.schur.grpObs) || upload(&d.grpRed, A.schur.grpRed) ||
-      upload(&d.schurRuns, A.schur.runs) || upload(&d.schurTasks, A.schur.tasks) || upload(&d.tileWorks, A.schur.works) ||
-      upload(&d.tileEnts, A.schur.ents))
+  if (m.put(&d.grpStart, A.schur.grpStart) || m.put(&d.grpObs, A.schur.grpObs) || m.put(&d.grpRed, A.schur.grpRed) ||
+      m.put(&d.schurRuns, A.schur.runs) || m.put(&d.schurTasks, A.schur.tasks) || m.put(&d.tileWorks, A.schur.works) ||
+      m.put(&d.tileEnts, A.schur.ents))
     return VB_E_HIP;
-  if (A.schur.hasClear && upload(&h->clearTilesD, A.schur.clearTiles)) return VB_E_HIP;
+  if (A.schur.hasClear && m.put(&h->clearTilesD, A.schur.clearTiles)) return VB_E_HIP;
   if (!h->shardTiles.empty() &&
-      (upload(&h->shardTilesD, h->shardTiles) || alloc0(&h->shardPack, h->shardTiles.size() * (size_t)TS * TS)))
+      (m.put(&h->shardTilesD, h->shardTiles) || m.zeroed(&h->shardPack, h->shardTiles.size() * (size_t)TS * TS)))
     return VB_E_HIP;
   // tiles, reduced vectors, pattern
-  if (upload(&d.tileIdx, A.pat.tileIdx) || alloc0(&d.tiles, (size_t)nTiles * TS * TS)) return VB_E_HIP;
+  if (m.put(&d.tileIdx, A.pat.tileIdx) || m.zeroed(&d.tiles, (size_t)nTiles * TS * TS)) return VB_E_HIP;
   const size_t nPad = (size_t)nT * TS;
-  if (alloc0(&d.gRed, nPad) || alloc0(&d.rhs, nPad) || alloc0(&d.xRed, nPad) || alloc0(&d.gRedNew, nPad) ||
-      alloc0(&d.stepRed, nPad) || alloc0(&d.stepPt, nPts * 3) || alloc0(&d.subRed, nPad) ||
-      alloc0(&d.subPt, nPts * 3) || alloc0(&h->yvec, nPad) || alloc0(&h->rhsWork, nPad))
+  if (m.zeroed(&d.gRed, nPad) || m.zeroed(&d.rhs, nPad) || m.zeroed(&d.xRed, nPad) || m.zeroed(&d.gRedNew, nPad) ||
+      m.zeroed(&d.stepRed, nPad) || m.zeroed(&d.stepPt, nPts * 3) || m.zeroed(&d.subRed, nPad) ||
+      m.zeroed(&d.subPt, nPts * 3) || m.zeroed(&h->yvec, nPad) || m.zeroed(&h->rhsWork, nPad))
     return VB_E_HIP;
-  if (upload(&h->colStartD, h->colStart) || upload(&h->rowStartD, h->rowStart) || alloc0(&h->solveFlags, 4 * (size_t)nT) ||
-      upload(&h->colTilesD, h->colTilesH) || upload(&h->colRowsD, h->colRowsH) || upload(&h->rowTilesD, h->rowTilesH) ||
-      upload(&h->rowColD, h->rowColH) || alloc0(&h->dinv, (size_t)(nT + 1) * 1024) ||
-      alloc0(&h->linv, (size_t)nT * TS * TS))
+  if (m.put(&h->colStartD, h->colStart) || m.put(&h->rowStartD, h->rowStart) || m.zeroed(&h->solveFlags, 4 * (size_t)nT) ||
+      m.put(&h->colTilesD, h->colTilesH) || m.put(&h->colRowsD, h->colRowsH) || m.put(&h->rowTilesD, h->rowTilesH) ||
+      m.put(&h->rowColD, h->rowColH) || m.zeroed(&h->dinv, (size_t)(nT + 1) * 1024) ||
+      m.zeroed(&h->linv, (size_t)nT * TS * TS))
     return VB_E_HIP;
   // schedules and their scratch (L_JJ of the fused levels)
   for (int i = 0; i < 2; i++) {
-    if (A.sch[i].built && uploadSched(A.sch[i], h->sch[i])) return VB_E_HIP;
-    if (A.sn[i].built && uploadSnSched(A.sn[i], h->sn[i])) return VB_E_HIP;
-    if (h->sch[i].nPtfDiag && !h->lscr && alloc0(&h->lscr, (size_t)nT * TS * TS)) return VB_E_HIP;
-    if (h->sn[i].nCopy && !h->lscrSn && alloc0(&h->lscrSn, 2 * (size_t)nT * TS * TS)) return VB_E_HIP;
+    if (A.sch[i].built && uploadSched(m, A.sch[i], h->sch[i])) return VB_E_HIP;
+    if (A.sn[i].built && uploadSnSched(m, A.sn[i], h->sn[i])) return VB_E_HIP;
+    if (h->sch[i].nPtfDiag && !h->lscr && m.zeroed(&h->lscr, (size_t)nT * TS * TS)) return VB_E_HIP;
+    if (h->sn[i].nCopy && !h->lscrSn && m.zeroed(&h->lscrSn, 2 * (size_t)nT * TS * TS)) return VB_E_HIP;
   }
   if (h->partSet) {
-    if (upload(&h->ownRowsD, A.part.ownRows) || alloc0(&h->ownPack, A.part.ownRows.size() * (size_t)TS + 1) ||
-        upload(&h->rootTilesD, h->rootTiles) || upload(&h->rootRowsD, h->rootRows) ||
-        alloc0(&h->rootPack, h->rootTiles.size() * (size_t)TS * TS + 1) ||
-        alloc0(&h->rowPack, h->rootRows.size() * (size_t)TS + 1))
+    if (m.put(&h->ownRowsD, A.part.ownRows) || m.zeroed(&h->ownPack, A.part.ownRows.size() * (size_t)TS + 1) ||
+        m.put(&h->rootTilesD, h->rootTiles) || m.put(&h->rootRowsD, h->rootRows) ||
+        m.zeroed(&h->rootPack, h->rootTiles.size() * (size_t)TS * TS + 1) ||
+        m.zeroed(&h->rowPack, h->rootRows.size() * (size_t)TS + 1))
       return VB_E_HIP;
   }
   // small factors
   for (int fk = 1; fk < 14; fk++)
-    if (upload(&d.sf[fk].vars, h->fvars[fk]) || upload(&d.sf[fk].consts, A.small.consts[fk])) return VB_E_HIP;
+    if (m.put(&d.sf[fk].vars, h->fvars[fk]) || m.put(&d.sf[fk].consts, A.small.consts[fk])) return VB_E_HIP;
   if ((h->isRoot || h->partSet) && d.nSmallStage > 0 &&
-      (alloc0(&d.sJ, (size_t)d.nSmallStage * kSmallJ) || alloc0(&d.sE, (size_t)d.nSmallStage * kSmallE) ||
-       alloc0(&d.sMeta, (size_t)d.nSmallStage * kSmallMeta)))
+      (m.zeroed(&d.sJ, (size_t)d.nSmallStage * kSmallJ) || m.zeroed(&d.sE, (size_t)d.nSmallStage * kSmallE) ||
+       m.zeroed(&d.sMeta, (size_t)d.nSmallStage * kSmallMeta)))
     return VB_E_HIP;
   // --recompute-preint inputs (preint.hip); PreintArgs holds them as pointers to const
   if (A.preint.present) {
     h->pi.n = (int64_t)h->piSrc.size();
-    if (upload(const_cast<PreintSrc**>(&h->pi.src), h->piSrc) || upload(const_cast<int64_t**>(&h->pi.t), A.preint.t) ||
-        upload(const_cast<double**>(&h->pi.v), A.preint.v) || upload(const_cast<int64_t**>(&h->pi.off), A.preint.off) ||
-        upload(const_cast<double**>(&h->pi.noise), A.preint.noise))
+    if (m.put(&h->pi.src, h->piSrc) || m.put(&h->pi.t, A.preint.t) || m.put(&h->pi.v, A.preint.v) ||
+        m.put(&h->pi.off, A.preint.off) || m.put(&h->pi.noise, A.preint.noise))
       return VB_E_HIP;
   }
   if (int rc = uploadRsTables(h)) return rc;
-  if (alloc0(&d.red, 64) || alloc0(&d.redS, 2 * 64 * 8) || alloc0(&d.err, 8)) return VB_E_HIP;
+  if (m.zeroed(&d.red, 64) || m.zeroed(&d.redS, 2 * 64 * 8) || m.zeroed(&d.err, 8)) return VB_E_HIP;
   return 0;
+}
+
+// what copyToHandle and uploadAll set, back to a created handle's values (the `fin` group released)
+void unfinalize(vb_handle h) {
+  h->d = Dev();
+  h->pi = PreintArgs();
+  for (int i = 0; i < 2; i++) h->sch[i] = Sched(), h->sn[i] = SnSched();
+  h->padRowsD = nullptr, h->clearTilesD = nullptr, h->shardTilesD = nullptr, h->shardPack = nullptr;
+  h->yvec = h->rhsWork = h->dinv = h->linv = h->lscr = h->lscrSn = nullptr;
+  h->colStartD = h->rowStartD = nullptr, h->solveFlags = nullptr;
+  h->colTilesD = h->colRowsD = h->rowTilesD = h->rowColD = nullptr;
+  h->ownRowsD = h->rootTilesD = h->rootRowsD = nullptr, h->ownPack = h->rootPack = h->rowPack = nullptr;
+  h->rvKind.clear(), h->rvHandle.clear(), h->rvDim.clear(), h->rvOff.clear(), h->lmOfPoint.clear(), h->colOwner.clear();
+  h->nRedReal = h->nParts = h->nParams = h->order = h->nPadRows = h->nLmObs = h->nClear = h->nTileEnt = h->nObEnt = 0;
+  h->tileFill.clear(), h->colStart.clear(), h->colTilesH.clear(), h->colRowsH.clear();
+  h->rowStart.clear(), h->rowTilesH.clear(), h->rowColH.clear();
+  h->tileFirst = h->tileCount = h->nOwnRows = h->nPairs = 0, h->nLevels = 0;
+  h->shardTiles.clear(), h->zeroRuns.clear(), h->rootTiles.clear(), h->rootRows.clear(), h->visRowOfPos.clear();
+  h->costRsB[0] = h->costRsB[1] = 0;
 }
 }  // namespace
 
@@ -222,10 +230,21 @@ int doFinalize(vb_handle h) {
                  h->partRank, h->partWorld, h->piSrc, h->imuT,  h->imuV,   h->piT,
                  h->piV,     h->piNoise, readKnobs(*h)};
   Symbolic A;
-  // an error leaves the handle as it was: nothing allocated, no field changed
+  // an error leaves the handle as it was: nothing allocated, no field changed (a second vb_finalize is legal)
   if (const Status e = analyze(in, A)) return fail(e.code, e.msg);
+  // the inputs that the results overwrite: the shard as given, the noise and the table offsets
+  const int64_t lmBegin = h->lmBegin, lmEnd = h->lmEnd;
+  const bool isRoot = h->isRoot;
+  const std::vector<double> piNoise = h->piNoise;
+  const std::vector<int64_t> rsOff = h->rsOff;
   copyToHandle(h, A);
-  if (int rc = uploadAll(h, A)) return rc;
+  if (uploadAll(h, A)) {
+    const int rc = devFail(h->fin, "vb_finalize: device allocation / copy");
+    h->fin.release();
+    unfinalize(h);
+    h->lmBegin = lmBegin, h->lmEnd = lmEnd, h->isRoot = isRoot, h->piNoise = piNoise, h->rsOff = rsOff;
+    return rc;
+  }
   h->finalized = true;
   return 0;
 }

@@ -2,7 +2,8 @@
 // solver.hip / ...), host helpers, the schedules and the handle (vb_handle_s).  api.hip: the numeric
 // phases and the LM controller; symbolic.hip: vb_finalize's host-only analysis (ordering, tile pattern,
 // Schur work lists, factorization schedules; symbolic.hpp); finalize.hip: its upload into the handle;
-// covariances.hip; multi.hip: the multi-process building blocks; tools.hip.
+// covariances.hip; multi.hip: the multi-process building blocks; tools.hip.  devmem.hpp: the owner of every
+// device buffer, pinned buffer, event and stream (the handle's lifetime groups, the per-call scratch).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -17,9 +18,11 @@
 #include <string>
 #include <unordered_map>
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "../../include/viba_hip.h"
+#include "devmem.hpp"
 #include "engine.hpp"
 #include "symbolic.hpp"
 
@@ -131,23 +134,15 @@ inline LossParams makeLoss(double a, double k) {
   return L;
 }
 
-template <typename T>
-int upload(T** dptr, const std::vector<T>& v) {
-  const size_t bytes = std::max<size_t>(1, v.size()) * sizeof(T);
-  HIPCHK(hipMalloc((void**)dptr, bytes));
-  if (!v.empty()) HIPCHK(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  // the engine's streams are non-blocking: they do not order behind the null stream the copy runs on
-  HIPCHK(hipStreamSynchronize(nullptr));
-  return 0;
+// a failed DevOwner request as the C-ABI's error
+template <class Owner>
+int devFail(const Owner& m, const std::string& what) {
+  return fail(VB_E_HIP, what + ": " + hipGetErrorString((hipError_t)m.lastError()));
 }
+// queue the read-back of dev[0, n) on st (nothing for a null host pointer)
 template <typename T>
-int alloc0(T** dptr, size_t n) {
-  HIPCHK(hipMalloc((void**)dptr, std::max<size_t>(1, n) * sizeof(T)));
-  HIPCHK(hipMemset(*dptr, 0, std::max<size_t>(1, n) * sizeof(T)));
-  // hipMemset may return before the clear lands, and the engine's non-blocking streams do not order
-  // behind it: a buffer allocated mid-run (the Gauss-Seidel pseudo-factor store) was once copied into
-  // before its clear ran, leaving zero diagonal tiles (a "Cholesky breakdown" only in long test runs)
-  HIPCHK(hipStreamSynchronize(nullptr));
+int download(T* host, const T* dev, size_t n, hipStream_t st) {
+  if (host && n) HIPCHK(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
   return 0;
 }
 
@@ -187,10 +182,25 @@ struct SnSched : SnSchedShape {
   hipGraphExec_t graph[2] = {nullptr, nullptr};
 };
 
-struct ReportState;  // report.hip
+// the residual report's device state (report.hip), made at its first call
+struct ReportState {
+  DevOwner mem;
+  int32_t* posOfRow = nullptr;  // visual factor row -> position of obCostOrder
+  int32_t* err = nullptr;       // bit 1: a rolling-shutter lookup out of range
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double histMs = 0.0;  // device time of the last vb_error_histogram's kernels
+};
 
 struct vb_handle_s {
   vb_config cfg;
+  // what the handle took from the HIP runtime, one owner per lifetime (devmem.hpp): a group is dropped as a
+  // unit, all of them with the handle, in reverse order (the streams of `create` last)
+  DevOwner create;  // vb_create: streams and events
+  DevOwner fin;     // everything doFinalize makes
+  DevOwner spec;    // specPrepare
+  DevOwner pcg;     // pcgPrepare: the PCG vectors and the preconditioners' stores
+  DevOwner refine;  // vb_refine_points
+  DevOwner prof;    // profEv
   hipStream_t st = nullptr;
   std::vector<double> data[9];
   std::vector<uint8_t> cst[9];
@@ -219,9 +229,9 @@ struct vb_handle_s {
   int32_t *refObsD = nullptr, *refPtD = nullptr;
   double *refBackD = nullptr, *refAccD = nullptr;
   // residual report (report.hip): the visual factor row (vb_add_factors order) at every position of
-  // obCostOrder, and the report's device state, made at its first call
+  // obCostOrder, and the report's device state
   std::vector<int32_t> visRowOfPos;
-  ReportState* rep = nullptr;
+  ReportState rep;
   double calibEvalMs = 0.0;  // device time of the last vb_calib_projection_offsets' kernels (calib_eval.hip)
   bool finalized = false;
   Dev d;

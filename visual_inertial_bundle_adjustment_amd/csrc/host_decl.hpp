@@ -19,8 +19,19 @@ int solveReduced(vb_handle h, int which = 0, int phases = 3);
 void backSubstitute(vb_handle h, int which);
 // vb_finalize (finalize.hip)
 int doFinalize(vb_handle h);
-// the residual report's device state (report.hip)
-void reportFree(vb_handle h);
+// is the whole problem on this handle (no landmark shard, no partition)?  vb_refine_points alone accepts a
+// vb_set_landmark_shard call that names every landmark on the root (shardCall = false)
+inline bool wholeProblem(vb_handle h, bool shardCall = true) {
+  return !(h->partSet || (shardCall && h->sharded) || h->d.lmB != 0 || h->d.lmE != h->d.nPts || !h->isRoot);
+}
+// capacity of a rolling-shutter table that is rebuilt on the device: the IMU samples (stamps t[0, n) [ns]) of
+// [mid - half, mid + half] [us] widened by 20 ms on both sides (the reference-time offsets of the calibration
+// move the gyro boundaries by far less), + 4
+inline int64_t rsTableCapacity(const int64_t* t, int64_t n, int64_t midUs, int64_t halfUs) {
+  const int64_t kWidenNs = 20000000;
+  const int64_t a = (midUs - halfUs) * 1000 - kWidenNs, b = (midUs + halfUs) * 1000 + kWidenNs;
+  return (std::upper_bound(t, t + n, b) - std::lower_bound(t, t + n, a)) + 4;
+}
 }  // namespace viba_host
 
 extern "C" {
@@ -39,7 +50,6 @@ void costStats(vb_handle h, const double* r, double* cost, vb_cost_stats* stats)
 // vb_optimize's speculation (optimize.hip)
 Dev specDev(vb_handle h);
 bool specPrepare(vb_handle h);
-void specRelease(vb_handle h);
 int specEnqueue(vb_handle h, int dontRetry, int p, bool early, bool rsDone = false, bool fuseCost = false);
 int specEarly(vb_handle h, bool cleared = false, bool storeCleared = false);
 void specCommit(vb_handle h);

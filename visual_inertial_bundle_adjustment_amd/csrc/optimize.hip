@@ -7,21 +7,6 @@
 
 extern "C" {
 // ---- vb_optimize's speculative linearization of the next iteration (vb_handle_s::tilesAlt ..)
-// Frees whatever specPrepare got before a failure (nothing has been swapped into h->d then).
-void specRelease(vb_handle h) {
-  for (void* p : {(void*)h->tilesAlt, (void*)h->cacheAlt, (void*)h->gRedAlt, (void*)h->rsSAlt, (void*)h->rsIAlt,
-                  (void*)h->rsGAlt, (void*)h->rsNAlt})
-    if (p) (void)hipFree(p);
-  h->tilesAlt = h->cacheAlt = h->gRedAlt = h->rsSAlt = h->rsIAlt = h->rsGAlt = nullptr;
-  h->rsNAlt = nullptr;
-  for (auto& row : h->evS)
-    for (hipEvent_t& e : row)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-  if (h->evCost) (void)hipEventDestroy(h->evCost), h->evCost = nullptr;
-  if (h->stR) (void)hipStreamDestroy(h->stR), h->stR = nullptr;
-  if (h->hostRed) (void)hipHostFree(h->hostRed), h->hostRed = nullptr;
-  (void)hipGetLastError();
-}
 // The spare tile store (nTiles x 32 KB: 2.2 GB at config C), ResultCache, gradient and rolling-shutter
 // tables of the speculative linearization, allocated at the first vb_optimize that speculates.  Returns
 // false when any of it cannot be had: the caller then runs the plain controller (no speculation), as
@@ -29,19 +14,25 @@ void specRelease(vb_handle h) {
 bool specPrepare(vb_handle h) {
   if (h->specReady) return true;
   Dev& d = h->d;
-  bool ok = !alloc0(&h->tilesAlt, (size_t)d.nTiles * TS * TS) && !alloc0(&h->cacheAlt, d.nObs) &&
-            !alloc0(&h->gRedAlt, (size_t)d.nT * TS) && !h->specFailDebug;
+  DevOwner& m = h->spec;
+  bool ok = !m.zeroed(&h->tilesAlt, (size_t)d.nTiles * TS * TS) && !m.zeroed(&h->cacheAlt, d.nObs) &&
+            !m.zeroed(&h->gRedAlt, (size_t)d.nT * TS) && !h->specFailDebug;
   if (ok && h->rsDevice) {
     const int64_t ns = h->rsOff[h->nRS];
-    ok = !alloc0(&h->rsSAlt, ns * 11) && !alloc0(&h->rsIAlt, (ns - h->nRS) * 9) &&
-         !alloc0(&h->rsGAlt, (size_t)h->nRS * 3) && !alloc0(&h->rsNAlt, h->nRS);
+    ok = !m.zeroed(&h->rsSAlt, ns * 11) && !m.zeroed(&h->rsIAlt, (ns - h->nRS) * 9) &&
+         !m.zeroed(&h->rsGAlt, (size_t)h->nRS * 3) && !m.zeroed(&h->rsNAlt, h->nRS);
   }
   for (auto& row : h->evS)
-    for (hipEvent_t& e : row) ok = ok && hipEventCreate(&e) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&h->evCost, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipStreamCreateWithFlags(&h->stR, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&h->hostRed, 32 * sizeof(double), hipHostMallocDefault) == hipSuccess;
-  if (!ok) specRelease(h);
+    for (hipEvent_t& e : row) ok = ok && !m.event(&e);
+  ok = ok && !m.event(&h->evCost, hipEventDisableTiming) && !m.stream(&h->stR) && !m.pinned(&h->hostRed, 32);
+  if (!ok) {  // give back what was had before the failure (nothing has been swapped into h->d then)
+    m.release();
+    h->tilesAlt = h->cacheAlt = h->gRedAlt = h->rsSAlt = h->rsIAlt = h->rsGAlt = h->hostRed = nullptr;
+    h->rsNAlt = nullptr, h->evCost = nullptr, h->stR = nullptr;
+    for (auto& row : h->evS)
+      for (hipEvent_t& e : row) e = nullptr;
+    (void)hipGetLastError();
+  }
   h->specReady = ok;
   return ok;
 }

@@ -42,63 +42,25 @@ __global__ void __launch_bounds__(256) bin_values_kernel(int64_t n, int m, const
 }  // namespace
 }  // namespace viba
 
-// the report's device state, made at the first call
-struct ReportState {
-  int32_t* posOfRow = nullptr;  // visual factor row -> position of obCostOrder
-  int32_t* err = nullptr;       // bit 1: a rolling-shutter lookup out of range
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double histMs = 0.0;  // device time of the last vb_error_histogram's kernels
-};
-
 namespace viba_host {
-
-void reportFree(vb_handle h) {
-  ReportState* r = h->rep;
-  if (!r) return;
-  if (r->posOfRow) hipFree(r->posOfRow);
-  if (r->err) hipFree(r->err);
-  for (hipEvent_t e : r->ev)
-    if (e) hipEventDestroy(e);
-  delete r;
-  h->rep = nullptr;
-}
-
 namespace {
 
 constexpr int kErrSize[14] = {2, 9, 9, 9, 3, 23, 17, 6, 6, 6, 23, 17, 6, 6};
 static_assert(VB_REPORT_MAX_GROUPS == kRepMaxGroups && VB_REPORT_MAX_EDGES == kRepMaxEdges, "caps of the LDS bin table");
 
-// frees its device buffers when the call returns, on every path
-struct Scratch {
-  std::vector<void*> p;
-  ~Scratch() {
-    for (void* q : p) hipFree(q);
-  }
-  template <typename T>
-  int get(T** out, size_t n) {
-    void* q = nullptr;
-    HIPCHK(hipMalloc(&q, std::max<size_t>(1, n) * sizeof(T)));
-    p.push_back(q);
-    *out = (T*)q;
-    return 0;
-  }
-};
-
 int reportCommon(vb_handle h, const char* what) {
   if (!h) return fail(VB_E_ARG, std::string(what) + ": null handle");
   if (!h->finalized) return fail(VB_E_STATE, std::string(what) + " before vb_finalize");
-  const Dev& d = h->d;
-  if (h->partSet || h->sharded || d.lmB != 0 || d.lmE != d.nPts || !h->isRoot)
+  if (!wholeProblem(h))
     return fail(VB_E_UNSUPPORTED, std::string(what) + " needs the whole problem on this handle (no shard / partition)");
   HIPCHK(hipSetDevice(h->cfg.device));
-  if (!h->rep) {
-    h->rep = new ReportState;
-    ReportState* r = h->rep;
+  ReportState& r = h->rep;
+  if (!r.posOfRow) {
     std::vector<int32_t> pos(h->visRowOfPos.size());
     for (size_t i = 0; i < pos.size(); i++) pos[h->visRowOfPos[i]] = (int32_t)i;
-    if (upload(&r->posOfRow, pos) || alloc0(&r->err, 2) || hipEventCreate(&r->ev[0]) != hipSuccess ||
-        hipEventCreate(&r->ev[1]) != hipSuccess) {
-      reportFree(h);  // a later call starts over instead of finding half a state
+    if (r.mem.put(&r.posOfRow, pos) || r.mem.zeroed(&r.err, 2) || r.mem.event(&r.ev[0]) || r.mem.event(&r.ev[1])) {
+      r.mem.release();  // a later call starts over instead of finding half a state
+      r.posOfRow = r.err = nullptr, r.ev[0] = r.ev[1] = nullptr;
       return fail(VB_E_HIP, std::string(what) + ": could not allocate the report's device state");
     }
   }
@@ -107,15 +69,9 @@ int reportCommon(vb_handle h, const char* what) {
 
 int checkReportErr(vb_handle h) {
   int32_t e = 0;
-  HIPCHK(hipMemcpyAsync(&e, h->rep->err, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(&e, h->rep.err, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
   if (e & 1) return fail(VB_E_RANGE, "RollingShutterData::getEstimate: out of range (residual report)");
-  return 0;
-}
-
-template <typename T>
-int download(T* host, const T* dev, size_t n, hipStream_t st) {
-  if (host && n) HIPCHK(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
   return 0;
 }
 
@@ -134,15 +90,15 @@ int vb_factor_errors(vb_handle h, int kind, int64_t first, int64_t n, double* ra
   if (first < 0 || n < 0 || first > N || n > N - first) return fail(VB_E_ARG, "vb_factor_errors: rows out of range");
   if (n == 0) return 0;
   const int m = kErrSize[kind];
-  Scratch S;
+  DevOwner S;  // frees its buffers when the call returns, on every path
   RepRows R;
   R.first = first, R.n = n;
   if ((raw && S.get(&R.raw, (size_t)n * m)) || (sq_unweighted && S.get(&R.squ, n)) ||
       (sq_weighted && S.get(&R.sqw, n)) || (cost && S.get(&R.cost, n)) ||
       (valid && kind == VB_F_VISUAL && S.get(&R.valid, n)))
-    return VB_E_HIP;
-  HIPCHK(hipMemsetAsync(h->rep->err, 0, sizeof(int32_t), h->st));
-  if (kind == VB_F_VISUAL) launch_visual_rows(h->d, h->rep->posOfRow, R, h->rep->err, h->st);
+    return devFail(S, "vb_factor_errors: device allocation");
+  HIPCHK(hipMemsetAsync(h->rep.err, 0, sizeof(int32_t), h->st));
+  if (kind == VB_F_VISUAL) launch_visual_rows(h->d, h->rep.posOfRow, R, h->rep.err, h->st);
   else launch_small_rows(h->d, kind, R, h->st);
   HIPCHK(hipGetLastError());
   if (download(raw, R.raw, (size_t)n * m, h->st) || download(sq_unweighted, R.squ, n, h->st) ||
@@ -180,14 +136,14 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
     }
   }
   const size_t nb = (size_t)n_groups * (n_edges + 1);
-  Scratch S;
+  DevOwner S;  // frees its buffers when the call returns, on every path
   RepHist H;
   H.which = which, H.nGroups = n_groups, H.nEdges = n_edges;
   uint8_t* grpD = nullptr;
   double* edgesD = nullptr;
   if (S.get(&edgesD, n_edges) || S.get(&H.counts, nb) || S.get(&H.cost, n_groups) || S.get(&H.nFactors, n_groups) ||
       S.get(&H.nFailing, n_groups) || (group_of_factor && S.get(&grpD, N)))
-    return VB_E_HIP;
+    return devFail(S, "vb_error_histogram: device allocation");
   H.edges = edgesD, H.grp = grpD;
   hipStream_t st = h->st;
   HIPCHK(hipMemcpyAsync(edgesD, edges, n_edges * sizeof(double), hipMemcpyHostToDevice, st));
@@ -196,30 +152,31 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
   HIPCHK(hipMemsetAsync(H.cost, 0, n_groups * sizeof(double), st));
   HIPCHK(hipMemsetAsync(H.nFactors, 0, n_groups * sizeof(unsigned long long), st));
   HIPCHK(hipMemsetAsync(H.nFailing, 0, n_groups * sizeof(unsigned long long), st));
-  HIPCHK(hipMemsetAsync(h->rep->err, 0, sizeof(int32_t), st));
-  HIPCHK(hipEventRecord(h->rep->ev[0], st));
+  HIPCHK(hipMemsetAsync(h->rep.err, 0, sizeof(int32_t), st));
+  HIPCHK(hipEventRecord(h->rep.ev[0], st));
   if (visual) {
     // a few workgroups per CU walk the positions: the table's flush is paid once per workgroup
-    launch_visual_hist(d, H, h->rep->err, h->numCUs * 8, st);
+    launch_visual_hist(d, H, h->rep.err, h->numCUs * 8, st);
   } else if (N > 0) {
     const int m = kErrSize[kind];
     RepRows R;
     R.first = 0, R.n = N;
-    if (S.get(&R.raw, (size_t)N * m) || S.get(&R.squ, N) || S.get(&R.sqw, N) || S.get(&R.cost, N)) return VB_E_HIP;
+    if (S.get(&R.raw, (size_t)N * m) || S.get(&R.squ, N) || S.get(&R.sqw, N) || S.get(&R.cost, N))
+      return devFail(S, "vb_error_histogram: device allocation");
     launch_small_rows(d, kind, R, st);
     hipLaunchKernelGGL(bin_values_kernel, dim3((unsigned)std::min<int64_t>((N + 255) / 256, 64)), dim3(256), 0, st, N, m,
                        R.raw, R.squ, R.sqw, R.cost, H);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->rep->ev[1], st));
+  HIPCHK(hipEventRecord(h->rep.ev[1], st));
   std::vector<unsigned long long> cnt(nb), nf(n_groups), nx(n_groups);
   if (download(cnt.data(), H.counts, nb, st) || download(nf.data(), H.nFactors, n_groups, st) ||
       download(nx.data(), H.nFailing, n_groups, st) || download(cost, H.cost, n_groups, st))
     return VB_E_HIP;
   if (int rc = checkReportErr(h)) return rc;
   float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->rep->ev[0], h->rep->ev[1]));
-  h->rep->histMs = ms;
+  HIPCHK(hipEventElapsedTime(&ms, h->rep.ev[0], h->rep.ev[1]));
+  h->rep.histMs = ms;
   if (counts) std::copy(cnt.begin(), cnt.end(), counts);
   if (n_factors) std::copy(nf.begin(), nf.end(), n_factors);
   if (n_failing) std::copy(nx.begin(), nx.end(), n_failing);
@@ -228,7 +185,7 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
 
 int vb_report_device_ms(vb_handle h, double* ms) {
   if (!h || !ms) return fail(VB_E_ARG, "vb_report_device_ms: null argument");
-  *ms = h->rep ? h->rep->histMs : 0.0;
+  *ms = h->rep.histMs;
   return 0;
 }
 

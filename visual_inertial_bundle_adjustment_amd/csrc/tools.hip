@@ -26,33 +26,19 @@ extern "C" int vb_rs_row_poses(int64_t n_imu, const int64_t* imu_t_ns, const dou
   for (int64_t i = 1; i < n_imu; i++)
     if (imu_t_ns[i] <= imu_t_ns[i - 1]) return fail(VB_E_ARG, "IMU timestamps must increase");
   if (n_obs == 0) return 0;
-  std::vector<void*> mem;
-  auto freeAll = [&] { for (void* p : mem) (void)hipFree(p); };
-  auto up = [&](auto** dst, const auto* src, size_t n) -> bool {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(*src)) != hipSuccess) return false;
-    mem.push_back(p);
-    *dst = (std::remove_cv_t<std::remove_reference_t<decltype(**dst)>>*)p;
-    return n == 0 || hipMemcpy(p, src, n * sizeof(*src), hipMemcpyHostToDevice) == hipSuccess;
-  };
-  auto zero = [&](auto** dst, size_t n) -> bool {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(**dst)) != hipSuccess) return false;
-    mem.push_back(p);
-    *dst = (std::remove_reference_t<decltype(*dst)>)p;
-    return hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(**dst)) == hipSuccess;
+  DevOwner m;  // frees everything when the call returns, on every path
+  // (copies on the null stream, blocking, as the kernels below)
+  auto up = [&](auto** dst, const auto* src, size_t n) { return !m.put(dst, src, n, nullptr); };
+  auto zero = [&](auto** dst, size_t n) {  // (cleared on the null stream, where the kernels run: no wait)
+    return !m.get(dst, n) && hipMemset(*dst, 0, std::max<size_t>(n, 1) * sizeof(**dst)) == hipSuccess;
   };
   Dev d{};
-  // tables: capacity as vb_finalize sizes them (the samples of [mid - half, mid + half] +- 20 ms, + 4)
+  // tables: capacity as vb_finalize sizes them (rsTableCapacity)
   std::vector<int64_t> off(n_rs + 1, 0);
   std::vector<double> v((size_t)n_imu * 6);
   for (int64_t i = 0; i < n_imu; i++)
     for (int k = 0; k < 3; k++) v[6 * i + k] = imu_gyro[3 * i + k], v[6 * i + 3 + k] = imu_accel[3 * i + k];
-  for (int32_t t = 0; t < n_rs; t++) {
-    const int64_t kWidenNs = 20000000;
-    const int64_t a = (rs_mid_us[t] - rs_half_us[t]) * 1000 - kWidenNs, b = (rs_mid_us[t] + rs_half_us[t]) * 1000 + kWidenNs;
-    off[t + 1] = off[t] + (std::upper_bound(imu_t_ns, imu_t_ns + n_imu, b) - std::lower_bound(imu_t_ns, imu_t_ns + n_imu, a)) + 4;
-  }
+  for (int32_t t = 0; t < n_rs; t++) off[t + 1] = off[t] + rsTableCapacity(imu_t_ns, n_imu, rs_mid_us[t], rs_half_us[t]);
   std::vector<int32_t> calibIdx(n_rs);
   std::iota(calibIdx.begin(), calibIdx.end(), 0);
   int32_t *oRig = nullptr, *oCam = nullptr, *rRS = nullptr;
@@ -68,16 +54,12 @@ extern "C" int vb_rs_row_poses(int64_t n_imu, const int64_t* imu_t_ns, const dou
          zero(&d.rsS, off[n_rs] * 11) && zero(&d.rsI, (off[n_rs] - n_rs) * 9) && zero(&d.rsG, (size_t)n_rs * 3) &&
          zero(&d.rsN, n_rs);
   }
-  if (!ok) {
-    freeAll();
-    return fail(VB_E_HIP, "vb_rs_row_poses: device allocation / copy failed");
-  }
+  if (!ok) return fail(VB_E_HIP, "vb_rs_row_poses: device allocation / copy failed");
   if (n_rs) launch_rs_build(d, nullptr);
   launch_rs_row_poses(d, n_obs, oRig, oCam, oRow, rPose, rVel, rRS, cams, out, nullptr);
   int32_t e[2] = {0, 0};
   const bool okRun = hipDeviceSynchronize() == hipSuccess && hipMemcpy(e, d.err, sizeof(e), hipMemcpyDeviceToHost) == hipSuccess &&
                      hipMemcpy(out_pose7, out, (size_t)n_obs * 7 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-  freeAll();
   if (!okRun) return fail(VB_E_HIP, "vb_rs_row_poses: kernel failed");
   if (e[1] & 1) return fail(VB_E_RANGE, "enumIntegrationSteps: IMU measurements do not cover a rolling-shutter interval");
   if (e[1] & 2) return fail(VB_E_NUMERIC, "RollingShutterData::compute: non-increasing sample times");
@@ -116,26 +98,11 @@ extern "C" int vb_triangulate_points(int64_t n_tracks, const int64_t* start, con
       return fail(VB_E_ARG, "vb_triangulate_points: camera record with an unknown model");
   if (device_ms) *device_ms = 0.0;
   if (n_tracks == 0) return 0;
-  std::vector<void*> mem;
+  DevOwner m;  // frees everything when the call returns, on every path
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto freeAll = [&] {
-    for (void* p : mem) (void)hipFree(p);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  };
-  auto up = [&](auto** dst, const auto* src, size_t n) -> bool {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(*src)) != hipSuccess) return false;
-    mem.push_back(p);
-    *dst = (std::remove_cv_t<std::remove_reference_t<decltype(**dst)>>*)p;
-    return n == 0 || hipMemcpy(p, src, n * sizeof(*src), hipMemcpyHostToDevice) == hipSuccess;
-  };
-  auto zero = [&](auto** dst, size_t n) -> bool {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(**dst)) != hipSuccess) return false;
-    mem.push_back(p);
-    *dst = (std::remove_reference_t<decltype(*dst)>)p;
-    return hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(**dst)) == hipSuccess;
+  auto up = [&](auto** dst, const auto* src, size_t n) { return !m.put(dst, src, n, nullptr); };
+  auto zero = [&](auto** dst, size_t n) {  // (cleared on the null stream, where the kernels run: no wait)
+    return !m.get(dst, n) && hipMemset(*dst, 0, std::max<size_t>(n, 1) * sizeof(**dst)) == hipSuccess;
   };
   int64_t* dStart = nullptr;
   int32_t *dSeed = nullptr, *dCam = nullptr;
@@ -145,11 +112,8 @@ extern "C" int vb_triangulate_points(int64_t n_tracks, const int64_t* start, con
   const bool okUp = up(&dStart, start, nt + 1) && up(&dSeed, seed, nt) && up(&dT, T_cam_world7, no * 7) &&
                     up(&dCam, obs_cam, no) && up(&dCams, cams24, (size_t)n_cams * 24) && up(&dUv, uv2, no * 2) &&
                     up(&dSh, sqrt_h4, no * 4) && zero(&dRays, no * 6) && zero(&dPt, nt * 3) && zero(&dOk, nt) &&
-                    zero(&dInl, no) && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-  if (!okUp) {
-    freeAll();
-    return fail(VB_E_HIP, "vb_triangulate_points: no HIP device, or device allocation / copy failed");
-  }
+                    zero(&dInl, no) && !m.event(&e0) && !m.event(&e1);
+  if (!okUp) return fail(VB_E_HIP, "vb_triangulate_points: no HIP device, or device allocation / copy failed");
   float ms = 0.f;
   bool okRun = hipEventRecord(e0, nullptr) == hipSuccess;
   launch_triangulate(n_tracks, n_obs, dStart, dSeed, dT, dCam, dCams, dUv, dSh, dRays, dPt, dOk, dInl, nullptr);
@@ -159,7 +123,6 @@ extern "C" int vb_triangulate_points(int64_t n_tracks, const int64_t* start, con
           hipMemcpy(point3, dPt, nt * 3 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
           hipMemcpy(ok, dOk, nt, hipMemcpyDeviceToHost) == hipSuccess &&
           (no == 0 || hipMemcpy(inlier, dInl, no, hipMemcpyDeviceToHost) == hipSuccess);
-  freeAll();
   if (!okRun) return fail(VB_E_HIP, "vb_triangulate_points: kernel failed");
   if (device_ms) *device_ms = ms;
   return 0;
@@ -171,12 +134,11 @@ extern "C" int vb_triangulate_points(int64_t n_tracks, const int64_t* start, con
 // which: 0 potrf, 1 trsm (one tile), 2/3 update (one pair)
 extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us) {
   if (!h || !h->finalized || iters <= 0) return fail(VB_E_STATE, "vb_bench_kernel needs a finalized handle");
+  DevOwner m;  // the scratch tiles and events of the call, freed on every path
   if (which >= 10) {  // kernels of the linearize / Schur phases alone, on the handle's own data
     Dev& d = h->d;
     hipEvent_t e0, e1, evP;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventCreateWithFlags(&evP, hipEventDisableTiming));
+    if (m.event(&e0) || m.event(&e1) || m.event(&evP, hipEventDisableTiming)) return devFail(m, "vb_bench_kernel: events");
     HIPCHK(hipStreamSynchronize(h->st));
     double total = 0;
     for (int it = 0; it < iters + 1; it++) {
@@ -237,7 +199,6 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
       HIPCHK(hipEventElapsedTime(&ms, e0, e1));
       if (it > 0) total += ms;
     }
-    hipEventDestroy(e0), hipEventDestroy(e1), hipEventDestroy(evP);
     if (avg_us) *avg_us = total * 1e3 / iters;
     // the timed launches left partial sums in the striped reduction slots (no fold_red after them) and
     // overwrote tiles, gradient and staging: clear the slots, and make the handle re-linearize before
@@ -260,26 +221,16 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
       A[j * TS + i] = s;
     }
   for (auto& v : B) v = rnd();
-  double *tiles = nullptr, *dinv = nullptr;
-  int32_t *colT = nullptr, *pairs = nullptr, *targ = nullptr;
-  HIPCHK(hipMalloc(&tiles, 4 * TS * TS * sizeof(double)));
-  HIPCHK(hipMalloc(&dinv, 2 * 1024 * sizeof(double)));
-  HIPCHK(hipMalloc(&colT, 4 * sizeof(int32_t)));
-  HIPCHK(hipMalloc(&pairs, 4 * sizeof(int32_t)));
-  HIPCHK(hipMalloc(&targ, sizeof(int32_t)));
   // potrf: tile 0 (col 0); trsm: diag 0 -> target 1; fan-in: 4 x (L_IK 1, L_JK 1) -> target 2 (plain)
   const int32_t ct[4] = {0, 0, 1, 0}, pr[4] = {2, 0, 4, 0}, tg[1] = {0};
   const int32_t fp[8] = {1, 1, 1, 1, 1, 1, 1, 1};
-  HIPCHK(hipMemcpy(colT, ct, sizeof(ct), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(pairs, pr, sizeof(pr), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(targ, tg, sizeof(tg), hipMemcpyHostToDevice));
-  int32_t* fpD = nullptr;
-  HIPCHK(hipMalloc(&fpD, sizeof(fp)));
-  HIPCHK(hipMemcpy(fpD, fp, sizeof(fp), hipMemcpyHostToDevice));
-  d.tiles = tiles;
+  double *tiles = nullptr, *dinv = nullptr;
+  int32_t *colT = nullptr, *pairs = nullptr, *targ = nullptr, *fpD = nullptr;
   hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
+  if (m.get(&tiles, 4 * TS * TS) || m.get(&dinv, 2 * 1024) || m.put(&colT, ct, 4, nullptr) || m.put(&pairs, pr, 4, nullptr) ||
+      m.put(&targ, tg, 1, nullptr) || m.put(&fpD, fp, 8, nullptr) || m.event(&e0) || m.event(&e1))
+    return devFail(m, "vb_bench_kernel: scratch");
+  d.tiles = tiles;
   double total = 0;
   const size_t tb = TS * TS * sizeof(double);
   for (int it = 0; it < iters + 1; it++) {
@@ -298,8 +249,6 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     if (it > 0) total += ms;  // first launch: warm-up
   }
-  hipEventDestroy(e0), hipEventDestroy(e1);
-  hipFree(tiles), hipFree(dinv), hipFree(colT), hipFree(pairs), hipFree(targ), hipFree(fpD);
   if (avg_us) *avg_us = total * 1e3 / iters;
   return 0;
 }

@@ -105,6 +105,20 @@ def _arr(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def live_resources(lib=None):
+    """(device bytes, pinned host bytes, events + streams) this process holds through the library, over every
+    handle and call (vb_debug_live_resources; the owners of csrc/devmem.hpp count them).  Needs no device."""
+    if lib is None:
+        from ._lib import load_hip_lib
+        lib = load_hip_lib()
+    out = (C.c_int64 * 3)()
+    lib.vb_debug_live_resources.restype = C.c_int
+    lib.vb_debug_live_resources.argtypes = [P]
+    if lib.vb_debug_live_resources(out) != 0:
+        raise VbError(-1, "vb_debug_live_resources")
+    return tuple(int(v) for v in out)
+
+
 def rs_row_poses(imu_t, imu_gyro, imu_accel, rs_mid, rs_half, rs_calib, gravity, rig_pose, rig_vel, rig_rs, cams,
                  obs_rig, obs_cam, obs_row, lib=None, name="vb_rs_row_poses"):
     """SingleSessionProblem::T_bodyImu_world_atImageRow (viba/problem/VisualFactor.cpp:303-327) of every
