@@ -291,8 +291,8 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
                                 double* p90, double* values, uint8_t* valid) {
   const char* what = "vb_calib_projection_offsets";
   if (!h) return fail(VB_E_ARG, std::string(what) + ": null handle");
-  if (!h->finalized) return fail(VB_E_STATE, std::string(what) + " before vb_finalize");
-  const Dev& d = h->d;
+  if (!h->fin) return fail(VB_E_STATE, std::string(what) + " before vb_finalize");
+  const Dev& d = h->fin->d;
   if (!wholeProblem(h))
     return fail(VB_E_UNSUPPORTED, std::string(what) + " needs the whole problem on this handle (no shard / partition)");
   if (n_dist <= 0 || !distances) return fail(VB_E_ARG, std::string(what) + ": n_dist must be positive");
@@ -318,8 +318,8 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
     for (double y = G.y0; y < hh; y += kCeStepY) G.ny++;
     maxGrid = std::max(maxGrid, G.nx * G.ny);
   }
-  const int64_t nIntr = (int64_t)h->data[VB_VAR_CAM_INTR].size() / VB_CAM_DATA;
-  const int64_t nExtr = (int64_t)h->data[VB_VAR_CAM_EXTR].size() / 7;
+  const int64_t nIntr = (int64_t)h->prob.data[VB_VAR_CAM_INTR].size() / VB_CAM_DATA;
+  const int64_t nExtr = (int64_t)h->prob.data[VB_VAR_CAM_EXTR].size() / 7;
   for (int64_t p = 0; p < n_pairs; p++) {
     if (cam_intr_var[p] < 0 || cam_intr_var[p] >= nIntr || cam_extr_var[p] < 0 || cam_extr_var[p] >= nExtr)
       return fail(VB_E_ARG, std::string(what) + ": camera variable index out of range");
@@ -331,7 +331,7 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
   }
   const size_t nSD = (size_t)n_series * n_dist;
   const double nan = std::numeric_limits<double>::quiet_NaN();
-  h->calibEvalMs = 0.0;
+  h->run.calibEvalMs = 0.0;
   if (n_pairs == 0 || maxGrid == 0) {  // no sample anywhere
     for (size_t i = 0; i < nSD; i++) {
       if (count) count[i] = 0;
@@ -348,7 +348,7 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
   const int64_t nBlk = n_pairs * A.bpp;
   if (nBlk * n_dist >= ((int64_t)1 << 31)) return fail(VB_E_ARG, std::string(what) + ": too many pairs for one call");
   HIPCHK(hipSetDevice(h->cfg.device));
-  hipStream_t st = h->st;
+  hipStream_t st = h->str.st;
   DevOwner S;  // frees its buffers and events when the call returns, on every path
   hipEvent_t ev[2] = {nullptr, nullptr};
   const size_t nFG = (size_t)n_fcam * maxGrid, nVal = (size_t)n_pairs * n_dist * maxGrid;
@@ -382,13 +382,13 @@ int vb_calib_projection_offsets(vb_handle h, int32_t n_fcam, const double* facto
   HIPCHK(hipStreamSynchronize(st));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  h->calibEvalMs = ms;
+  h->run.calibEvalMs = ms;
   return 0;
 }
 
 int vb_calib_eval_device_ms(vb_handle h, double* ms) {
   if (!h || !ms) return fail(VB_E_ARG, "vb_calib_eval_device_ms: null argument");
-  *ms = h->calibEvalMs;
+  *ms = h->run.calibEvalMs;
   return 0;
 }
 

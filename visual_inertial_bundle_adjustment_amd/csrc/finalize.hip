@@ -1,5 +1,6 @@
-// vb_finalize: run the host-only symbolic analysis (symbolic.hip) on what the handle holds, then copy
-// its results into the handle and upload them.  No ordering, pattern or schedule logic lives here.
+// vb_finalize: run the host-only symbolic analysis (symbolic.hip) on the handle's Problem, upload its results
+// through a local Finalized (host.hpp), move the host-side results it keeps into it, and install it in the
+// handle.  No ordering, pattern or schedule logic lives here.
 #include "host.hpp"
 
 namespace viba_host {
@@ -11,36 +12,35 @@ Knobs readKnobs(const vb_handle_s& h) {
   if (const char* e = getenv("VIBA_ND_CUTWIN")) k.cutWin = std::max(0.0, std::min(0.45, atof(e)));
   if (const char* e = getenv("VIBA_ND_LEAF")) k.leafDims = std::max<int64_t>(64, atoll(e));
   k.stats = getenv("VIBA_STATS") != nullptr;
-  k.ptFuseMax = h.ptFuseMax, k.useSn = h.useSn, k.snStreams = h.snStreams;
+  k.ptFuseMax = h.tune.ptFuseMax, k.useSn = h.tune.useSn, k.snStreams = h.tune.snStreams;
   return k;
 }
 
 int uploadSched(DevOwner& m, const SchedHost& H, Sched& S) {
   static_cast<SchedShape&>(S) = H;
-  if (m.put(&S.potrfTileD, H.potrfTile) || m.put(&S.potrfColD, H.potrfCol) || m.put(&S.trsmDiagD, H.trsmDiag) ||
-      m.put(&S.trsmTargetD, H.trsmTarget) || m.put(&S.trsmColD, H.trsmCol) || m.put(&S.trsmRowD, H.trsmRow) ||
-      m.put(&S.updD, H.upd) || m.put(&S.fanPairsD, H.fanPairs) || m.put(&S.tasksFD, H.tasksF) ||
-      m.put(&S.tasksBD, H.tasksB) || m.put(&S.expFD, H.expF) || m.put(&S.expBD, H.expB) ||
-      m.put(&S.preReadyD, H.preReady) || m.put(&S.ptfD, H.ptf) || m.put(&S.ptfDiagD, H.ptfDiag))
-    return VB_E_HIP;
-  return 0;
+  const bool bad = m.put(&S.potrfTileD, H.potrfTile) || m.put(&S.potrfColD, H.potrfCol) || m.put(&S.trsmDiagD, H.trsmDiag) ||
+                   m.put(&S.trsmTargetD, H.trsmTarget) || m.put(&S.trsmColD, H.trsmCol) || m.put(&S.trsmRowD, H.trsmRow) ||
+                   m.put(&S.updD, H.upd) || m.put(&S.fanPairsD, H.fanPairs) || m.put(&S.tasksFD, H.tasksF) ||
+                   m.put(&S.tasksBD, H.tasksB) || m.put(&S.expFD, H.expF) || m.put(&S.expBD, H.expB) ||
+                   m.put(&S.preReadyD, H.preReady) || m.put(&S.ptfD, H.ptf) || m.put(&S.ptfDiagD, H.ptfDiag);
+  return bad ? VB_E_HIP : 0;
 }
 
 int uploadSnSched(DevOwner& m, const SnSchedHost& H, SnSched& S) {
   static_cast<SnSchedShape&>(S) = H;
-  if (m.put(&S.updD, H.upd) || m.put(&S.fanPairsD, H.fanPairs) || m.put(&S.potD, H.pot) || m.put(&S.rowD, H.row) ||
-      m.put(&S.fusD, H.fus) || m.put(&S.copyD, H.copy) || m.put(&S.invEarlyD, H.invEarly) ||
-      m.put(&S.invLateD, H.invLate))
-    return VB_E_HIP;
-  return 0;
+  const bool bad = m.put(&S.updD, H.upd) || m.put(&S.fanPairsD, H.fanPairs) || m.put(&S.potD, H.pot) ||
+                   m.put(&S.rowD, H.row) || m.put(&S.fusD, H.fus) || m.put(&S.copyD, H.copy) ||
+                   m.put(&S.invEarlyD, H.invEarly) || m.put(&S.invLateD, H.invLate);
+  return bad ? VB_E_HIP : 0;
 }
 
-// the host-side results the handle keeps, and the Dev scalars
-void copyToHandle(vb_handle h, const Symbolic& A) {
-  Dev& d = h->d;
-  d.jac = makeJac(h->cfg.imu_calib_options);
-  d.reproj = makeLoss(h->cfg.reproj_loss_radius, h->cfg.reproj_loss_cutoff);
-  d.imu = makeLoss(h->cfg.imu_loss_radius, h->cfg.imu_loss_cutoff);
+// the Dev scalars and the counts of the analysis
+void setScalars(const vb_handle_s& h, const Symbolic& A, Finalized& f) {
+  const Problem& P = h.prob;
+  Dev& d = f.d;
+  d.jac = makeJac(h.cfg.imu_calib_options);
+  d.reproj = makeLoss(h.cfg.reproj_loss_radius, h.cfg.reproj_loss_cutoff);
+  d.imu = makeLoss(h.cfg.imu_loss_radius, h.cfg.imu_loss_cutoff);
   d.T = TS;
   for (int k = 0; k < 9; k++) d.nvar[k] = A.reg.nvar[k];
   const int64_t nPts = A.reg.nPts;
@@ -54,78 +54,74 @@ void copyToHandle(vb_handle h, const Symbolic& A) {
   d.nTileWorks = (int64_t)A.schur.works.size();
   for (int fk = 1; fk < 14; fk++) {
     SmallFactors& sf = d.sf[fk];
-    sf.nv = kNumVars[fk], sf.n = (int64_t)h->fint[fk].size(), sf.nc = A.small.nc[fk], sf.stage = A.small.stage[fk];
+    sf.nv = kNumVars[fk], sf.n = (int64_t)P.fint[fk].size(), sf.nc = A.small.nc[fk], sf.stage = A.small.stage[fk];
   }
   d.nSmallStage = A.small.nSmallStage;
-  d.myRank = h->partRank, d.world = h->partWorld;
-  d.nRS = h->nRS;
+  d.myRank = P.partRank, d.world = P.partWorld;
+  d.nRS = P.nRS;
 
-  h->rvKind = A.lay.rvKind, h->rvHandle = A.lay.rvHandle, h->rvDim = A.lay.rvDim, h->rvOff = A.lay.rvOff;
-  h->lmOfPoint = A.reg.lmOfPoint;
-  h->colOwner = A.lay.colOwner;
-  h->nRedReal = A.lay.nRedReal, h->nParts = (int64_t)A.nd.partBegin.size();
-  h->nParams = nPts + A.lay.nRV;
-  h->order = nPts * 3 + A.lay.nRedReal;
-  h->nPadRows = (int64_t)A.lay.padRows.size();
-  h->nLmObs = A.obs.lmObs[nPts];
-  h->lmBegin = A.shard.lmBegin, h->lmEnd = A.shard.lmEnd, h->isRoot = A.shard.isRoot;
-  h->tileFill = A.pat.tileFill;
-  h->colStart = A.pat.colStart, h->colTilesH = A.pat.colTiles, h->colRowsH = A.pat.colRows;
-  h->rowStart = A.pat.rowStart, h->rowTilesH = A.pat.rowTiles, h->rowColH = A.pat.rowCol;
-  h->nClear = (int64_t)A.schur.clearTiles.size();
-  h->nTileEnt = (int64_t)A.schur.ents.size(), h->nObEnt = d.nGroups;
-  h->tileFirst = A.schur.tileFirst, h->tileCount = A.schur.tileCount;
-  h->shardTiles = A.schur.shardTiles;
-  h->zeroRuns = A.part.zeroRuns, h->rootTiles = A.part.rootTiles, h->rootRows = A.part.rootRows;
-  h->nOwnRows = (int64_t)A.part.ownRows.size();
-  h->nLevels = A.pat.nLevels;
-  h->nPairs = A.sch[0].nPairs + A.sch[1].nPairs;
-  h->costRsB[0] = A.cost.rsBegin[0], h->costRsB[1] = A.cost.rsBegin[1];
-  h->visRowOfPos.resize(A.cost.order.size());
-  for (size_t i = 0; i < A.cost.order.size(); i++) h->visRowOfPos[i] = (int32_t)A.obs.perm[A.cost.order[i]];
-  if (A.preint.present) h->piNoise = A.preint.noise;
+  f.nParams = nPts + A.lay.nRV, f.order = nPts * 3 + A.lay.nRedReal;
+  f.nClear = (int64_t)A.schur.clearTiles.size(), f.nTileEnt = (int64_t)A.schur.ents.size();
+  f.tileFirst = A.schur.tileFirst, f.tileCount = A.schur.tileCount;
+  f.nLevels = A.pat.nLevels, f.nPairs = A.sch[0].nPairs + A.sch[1].nPairs;
+  f.costRsB[0] = A.cost.rsBegin[0], f.costRsB[1] = A.cost.rsBegin[1];
+}
+
+// the host-side results read after vb_finalize, moved out of the analysis (the large lists nobody reads
+// again -- tileIdx, the Schur entries and works, the observation arrays -- go with it)
+void keepResults(Symbolic& A, Finalized& f) {
+  f.visRowOfPos.resize(A.cost.order.size());
+  for (size_t i = 0; i < A.cost.order.size(); i++) f.visRowOfPos[i] = (int32_t)A.obs.perm[A.cost.order[i]];
+  f.lay = std::move(A.lay), f.shard = std::move(A.shard), f.part = std::move(A.part);
+  f.lmOfPoint = std::move(A.reg.lmOfPoint);
+  f.tileFill = std::move(A.pat.tileFill);
+  f.colStart = std::move(A.pat.colStart), f.colTilesH = std::move(A.pat.colTiles), f.colRowsH = std::move(A.pat.colRows);
+  f.rowStart = std::move(A.pat.rowStart), f.rowColH = std::move(A.pat.rowCol);
+  f.shardTiles = std::move(A.schur.shardTiles);
+  if (A.preint.present) f.piNoise = std::move(A.preint.noise);
 }
 
 // the rolling-shutter tables: rebuilt on the device (capacities from the IMU stream), or as given
-int uploadRsTables(vb_handle h) {
-  Dev& d = h->d;
-  DevOwner& m = h->fin;
-  if (h->rsDevice) {
-    h->rsOff.assign(h->nRS + 1, 0);
-    for (int32_t t = 0; t < h->nRS; t++)
-      h->rsOff[t + 1] = h->rsOff[t] + rsTableCapacity(h->imuT.data(), (int64_t)h->imuT.size(), h->rsMid[t], h->rsHalf[t]);
-    const int64_t ns = h->rsOff[h->nRS];
-    std::vector<int32_t> zeroN(h->nRS, 0);
-    if (m.put(&d.rsOff, h->rsOff) || m.zeroed(&d.rsS, ns * 11) || m.zeroed(&d.rsI, (ns - h->nRS) * 9) ||
-        m.zeroed(&d.rsG, (size_t)h->nRS * 3) || m.put(&d.rsN, zeroN) || m.put(&d.imuT, h->imuT) ||
-        m.put(&d.imuV, h->imuV) || m.put(&d.rsMid, h->rsMid) || m.put(&d.rsHalf, h->rsHalf) ||
-        m.put(&d.rsCalib, h->rsCalib))
+int uploadRsTables(const Problem& P, Finalized& f) {
+  Dev& d = f.d;
+  DevOwner& m = f.mem;
+  if (P.rsDevice) {
+    f.rsOff.assign(P.nRS + 1, 0);
+    for (int32_t t = 0; t < P.nRS; t++)
+      f.rsOff[t + 1] = f.rsOff[t] + rsTableCapacity(P.imuT.data(), (int64_t)P.imuT.size(), P.rsMid[t], P.rsHalf[t]);
+    const int64_t ns = f.rsOff[P.nRS];
+    std::vector<int32_t> zeroN(P.nRS, 0);
+    if (m.put(&d.rsOff, f.rsOff) || m.zeroed(&d.rsS, ns * 11) || m.zeroed(&d.rsI, (ns - P.nRS) * 9) ||
+        m.zeroed(&d.rsG, (size_t)P.nRS * 3) || m.put(&d.rsN, zeroN) || m.put(&d.imuT, P.imuT) ||
+        m.put(&d.imuV, P.imuV) || m.put(&d.rsMid, P.rsMid) || m.put(&d.rsHalf, P.rsHalf) ||
+        m.put(&d.rsCalib, P.rsCalib))
       return VB_E_HIP;
-    d.nImu = (int64_t)h->imuT.size();
-    d.rsGravVar = h->rsGravVar;
+    d.nImu = (int64_t)P.imuT.size();
+    d.rsGravVar = P.rsGravVar;
     return 0;
   }
-  std::vector<int32_t> cnt(h->nRS);
-  for (int32_t t = 0; t < h->nRS; t++) cnt[t] = (int32_t)(h->rsOff[t + 1] - h->rsOff[t]);
-  if (h->rsOff.empty()) h->rsOff.assign(1, 0);
-  if (m.put(&d.rsOff, h->rsOff) || m.put(&d.rsS, h->rsS) || m.put(&d.rsI, h->rsI) || m.put(&d.rsG, h->rsG) ||
+  f.rsOff = P.rsOff;
+  std::vector<int32_t> cnt(P.nRS);
+  for (int32_t t = 0; t < P.nRS; t++) cnt[t] = (int32_t)(f.rsOff[t + 1] - f.rsOff[t]);
+  if (f.rsOff.empty()) f.rsOff.assign(1, 0);
+  if (m.put(&d.rsOff, f.rsOff) || m.put(&d.rsS, P.rsS) || m.put(&d.rsI, P.rsI) || m.put(&d.rsG, P.rsG) ||
       m.put(&d.rsN, cnt))
     return VB_E_HIP;
   return 0;
 }
 
-// every device buffer of vb_finalize, owned by the handle's `fin` group
-int uploadAll(vb_handle h, const Symbolic& A) {
-  Dev& d = h->d;
-  DevOwner& m = h->fin;
+// every device buffer of vb_finalize, owned by f.mem
+int uploadAll(const Problem& P, const Symbolic& A, Finalized& f) {
+  Dev& d = f.d;
+  DevOwner& m = f.mem;
   const int64_t nPts = A.reg.nPts, nObs = A.obs.nObs, nTiles = A.pat.nTiles;
   const int32_t nT = A.lay.nT;
   // variables and the reduced layout
   for (int k = 0; k < 9; k++)
-    if (m.put(&d.var[k], h->data[k]) || m.zeroed(&d.varBak[k], h->data[k].size()) || m.put(&d.redOf[k], A.lay.redOf[k]))
+    if (m.put(&d.var[k], P.data[k]) || m.zeroed(&d.varBak[k], P.data[k].size()) || m.put(&d.redOf[k], A.lay.redOf[k]))
       return VB_E_HIP;
   if (m.put(&d.rvKind, A.lay.rvKind) || m.put(&d.rvHandle, A.lay.rvHandle) || m.put(&d.rvDim, A.lay.rvDim) ||
-      m.put(&d.rvOff, A.lay.rvOff) || m.put(&d.rvRowEnd, A.pat.rowEnd) || m.put(&h->padRowsD, A.lay.padRows))
+      m.put(&d.rvOff, A.lay.rvOff) || m.put(&d.rvRowEnd, A.pat.rowEnd) || m.put(&f.padRowsD, A.lay.padRows))
     return VB_E_HIP;
   if (m.put(&d.colOwner, A.lay.colOwner)) return VB_E_HIP;
   // observations
@@ -155,97 +151,72 @@ int uploadAll(vb_handle h, const Symbolic& A) {
       m.put(&d.schurRuns, A.schur.runs) || m.put(&d.schurTasks, A.schur.tasks) || m.put(&d.tileWorks, A.schur.works) ||
       m.put(&d.tileEnts, A.schur.ents))
     return VB_E_HIP;
-  if (A.schur.hasClear && m.put(&h->clearTilesD, A.schur.clearTiles)) return VB_E_HIP;
-  if (!h->shardTiles.empty() &&
-      (m.put(&h->shardTilesD, h->shardTiles) || m.zeroed(&h->shardPack, h->shardTiles.size() * (size_t)TS * TS)))
+  if (A.schur.hasClear && m.put(&f.clearTilesD, A.schur.clearTiles)) return VB_E_HIP;
+  if (!A.schur.shardTiles.empty() &&
+      (m.put(&f.shardTilesD, A.schur.shardTiles) || m.zeroed(&f.shardPack, A.schur.shardTiles.size() * (size_t)TS * TS)))
     return VB_E_HIP;
   // tiles, reduced vectors, pattern
   if (m.put(&d.tileIdx, A.pat.tileIdx) || m.zeroed(&d.tiles, (size_t)nTiles * TS * TS)) return VB_E_HIP;
   const size_t nPad = (size_t)nT * TS;
   if (m.zeroed(&d.gRed, nPad) || m.zeroed(&d.rhs, nPad) || m.zeroed(&d.xRed, nPad) || m.zeroed(&d.gRedNew, nPad) ||
       m.zeroed(&d.stepRed, nPad) || m.zeroed(&d.stepPt, nPts * 3) || m.zeroed(&d.subRed, nPad) ||
-      m.zeroed(&d.subPt, nPts * 3) || m.zeroed(&h->yvec, nPad) || m.zeroed(&h->rhsWork, nPad))
+      m.zeroed(&d.subPt, nPts * 3) || m.zeroed(&f.yvec, nPad) || m.zeroed(&f.rhsWork, nPad))
     return VB_E_HIP;
-  if (m.put(&h->colStartD, h->colStart) || m.put(&h->rowStartD, h->rowStart) || m.zeroed(&h->solveFlags, 4 * (size_t)nT) ||
-      m.put(&h->colTilesD, h->colTilesH) || m.put(&h->colRowsD, h->colRowsH) || m.put(&h->rowTilesD, h->rowTilesH) ||
-      m.put(&h->rowColD, h->rowColH) || m.zeroed(&h->dinv, (size_t)(nT + 1) * 1024) ||
-      m.zeroed(&h->linv, (size_t)nT * TS * TS))
+  if (m.put(&f.colStartD, A.pat.colStart) || m.put(&f.rowStartD, A.pat.rowStart) || m.zeroed(&f.solveFlags, 4 * (size_t)nT) ||
+      m.put(&f.colTilesD, A.pat.colTiles) || m.put(&f.colRowsD, A.pat.colRows) || m.put(&f.rowTilesD, A.pat.rowTiles) ||
+      m.put(&f.rowColD, A.pat.rowCol) || m.zeroed(&f.dinv, (size_t)(nT + 1) * 1024) ||
+      m.zeroed(&f.linv, (size_t)nT * TS * TS))
     return VB_E_HIP;
   // schedules and their scratch (L_JJ of the fused levels)
   for (int i = 0; i < 2; i++) {
-    if (A.sch[i].built && uploadSched(m, A.sch[i], h->sch[i])) return VB_E_HIP;
-    if (A.sn[i].built && uploadSnSched(m, A.sn[i], h->sn[i])) return VB_E_HIP;
-    if (h->sch[i].nPtfDiag && !h->lscr && m.zeroed(&h->lscr, (size_t)nT * TS * TS)) return VB_E_HIP;
-    if (h->sn[i].nCopy && !h->lscrSn && m.zeroed(&h->lscrSn, 2 * (size_t)nT * TS * TS)) return VB_E_HIP;
+    if (A.sch[i].built && uploadSched(m, A.sch[i], f.sch[i])) return VB_E_HIP;
+    if (A.sn[i].built && uploadSnSched(m, A.sn[i], f.sn[i])) return VB_E_HIP;
+    if (f.sch[i].nPtfDiag && !f.lscr && m.zeroed(&f.lscr, (size_t)nT * TS * TS)) return VB_E_HIP;
+    if (f.sn[i].nCopy && !f.lscrSn && m.zeroed(&f.lscrSn, 2 * (size_t)nT * TS * TS)) return VB_E_HIP;
   }
-  if (h->partSet) {
-    if (m.put(&h->ownRowsD, A.part.ownRows) || m.zeroed(&h->ownPack, A.part.ownRows.size() * (size_t)TS + 1) ||
-        m.put(&h->rootTilesD, h->rootTiles) || m.put(&h->rootRowsD, h->rootRows) ||
-        m.zeroed(&h->rootPack, h->rootTiles.size() * (size_t)TS * TS + 1) ||
-        m.zeroed(&h->rowPack, h->rootRows.size() * (size_t)TS + 1))
+  if (P.partSet) {
+    if (m.put(&f.ownRowsD, A.part.ownRows) || m.zeroed(&f.ownPack, A.part.ownRows.size() * (size_t)TS + 1) ||
+        m.put(&f.rootTilesD, A.part.rootTiles) || m.put(&f.rootRowsD, A.part.rootRows) ||
+        m.zeroed(&f.rootPack, A.part.rootTiles.size() * (size_t)TS * TS + 1) ||
+        m.zeroed(&f.rowPack, A.part.rootRows.size() * (size_t)TS + 1))
       return VB_E_HIP;
   }
   // small factors
   for (int fk = 1; fk < 14; fk++)
-    if (m.put(&d.sf[fk].vars, h->fvars[fk]) || m.put(&d.sf[fk].consts, A.small.consts[fk])) return VB_E_HIP;
-  if ((h->isRoot || h->partSet) && d.nSmallStage > 0 &&
+    if (m.put(&d.sf[fk].vars, P.fvars[fk]) || m.put(&d.sf[fk].consts, A.small.consts[fk])) return VB_E_HIP;
+  if ((A.shard.isRoot || P.partSet) && d.nSmallStage > 0 &&
       (m.zeroed(&d.sJ, (size_t)d.nSmallStage * kSmallJ) || m.zeroed(&d.sE, (size_t)d.nSmallStage * kSmallE) ||
        m.zeroed(&d.sMeta, (size_t)d.nSmallStage * kSmallMeta)))
     return VB_E_HIP;
   // --recompute-preint inputs (preint.hip); PreintArgs holds them as pointers to const
   if (A.preint.present) {
-    h->pi.n = (int64_t)h->piSrc.size();
-    if (m.put(&h->pi.src, h->piSrc) || m.put(&h->pi.t, A.preint.t) || m.put(&h->pi.v, A.preint.v) ||
-        m.put(&h->pi.off, A.preint.off) || m.put(&h->pi.noise, A.preint.noise))
+    f.pi.n = (int64_t)P.piSrc.size();
+    if (m.put(&f.pi.src, P.piSrc) || m.put(&f.pi.t, A.preint.t) || m.put(&f.pi.v, A.preint.v) ||
+        m.put(&f.pi.off, A.preint.off) || m.put(&f.pi.noise, A.preint.noise))
       return VB_E_HIP;
   }
-  if (int rc = uploadRsTables(h)) return rc;
+  if (int rc = uploadRsTables(P, f)) return rc;
   if (m.zeroed(&d.red, 64) || m.zeroed(&d.redS, 2 * 64 * 8) || m.zeroed(&d.err, 8)) return VB_E_HIP;
   return 0;
 }
 
-// what copyToHandle and uploadAll set, back to a created handle's values (the `fin` group released)
-void unfinalize(vb_handle h) {
-  h->d = Dev();
-  h->pi = PreintArgs();
-  for (int i = 0; i < 2; i++) h->sch[i] = Sched(), h->sn[i] = SnSched();
-  h->padRowsD = nullptr, h->clearTilesD = nullptr, h->shardTilesD = nullptr, h->shardPack = nullptr;
-  h->yvec = h->rhsWork = h->dinv = h->linv = h->lscr = h->lscrSn = nullptr;
-  h->colStartD = h->rowStartD = nullptr, h->solveFlags = nullptr;
-  h->colTilesD = h->colRowsD = h->rowTilesD = h->rowColD = nullptr;
-  h->ownRowsD = h->rootTilesD = h->rootRowsD = nullptr, h->ownPack = h->rootPack = h->rowPack = nullptr;
-  h->rvKind.clear(), h->rvHandle.clear(), h->rvDim.clear(), h->rvOff.clear(), h->lmOfPoint.clear(), h->colOwner.clear();
-  h->nRedReal = h->nParts = h->nParams = h->order = h->nPadRows = h->nLmObs = h->nClear = h->nTileEnt = h->nObEnt = 0;
-  h->tileFill.clear(), h->colStart.clear(), h->colTilesH.clear(), h->colRowsH.clear();
-  h->rowStart.clear(), h->rowTilesH.clear(), h->rowColH.clear();
-  h->tileFirst = h->tileCount = h->nOwnRows = h->nPairs = 0, h->nLevels = 0;
-  h->shardTiles.clear(), h->zeroRuns.clear(), h->rootTiles.clear(), h->rootRows.clear(), h->visRowOfPos.clear();
-  h->costRsB[0] = h->costRsB[1] = 0;
-}
 }  // namespace
 
 int doFinalize(vb_handle h) {
-  const Input in{h->data,    h->cst,     h->fvars,    h->fint,  h->fconst, h->cfg.imu_calib_options,
-                 h->nRS,     h->sharded, h->lmBegin,  h->lmEnd, h->isRoot, h->partSet,
-                 h->partRank, h->partWorld, h->piSrc, h->imuT,  h->imuV,   h->piT,
-                 h->piV,     h->piNoise, readKnobs(*h)};
+  const Problem& P = h->prob;
+  const Input in{P.data,     P.cst,     P.fvars,   P.fint,  P.fconst, h->cfg.imu_calib_options,
+                 P.nRS,      P.sharded, P.lmBegin, P.lmEnd, P.isRoot, P.partSet,
+                 P.partRank, P.partWorld, P.piSrc, P.imuT,  P.imuV,   P.piT,
+                 P.piV,      P.piNoise, readKnobs(*h)};
   Symbolic A;
-  // an error leaves the handle as it was: nothing allocated, no field changed (a second vb_finalize is legal)
   if (const Status e = analyze(in, A)) return fail(e.code, e.msg);
-  // the inputs that the results overwrite: the shard as given, the noise and the table offsets
-  const int64_t lmBegin = h->lmBegin, lmEnd = h->lmEnd;
-  const bool isRoot = h->isRoot;
-  const std::vector<double> piNoise = h->piNoise;
-  const std::vector<int64_t> rsOff = h->rsOff;
-  copyToHandle(h, A);
-  if (uploadAll(h, A)) {
-    const int rc = devFail(h->fin, "vb_finalize: device allocation / copy");
-    h->fin.release();
-    unfinalize(h);
-    h->lmBegin = lmBegin, h->lmEnd = lmEnd, h->isRoot = isRoot, h->piNoise = piNoise, h->rsOff = rsOff;
-    return rc;
-  }
-  h->finalized = true;
+  // built beside the handle and installed whole: a failure drops f with everything it took, and the handle
+  // is the created handle it was (a second vb_finalize is legal)
+  auto f = std::make_unique<Finalized>();
+  setScalars(*h, A, *f);
+  if (uploadAll(P, A, *f)) return devFail(f->mem, "vb_finalize: device allocation / copy");
+  keepResults(A, *f);
+  h->fin = std::move(f);
   return 0;
 }
 

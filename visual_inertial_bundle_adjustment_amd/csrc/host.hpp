@@ -1,9 +1,9 @@
 // Host side of the HIP LM engine, shared by its translation units: the kernel launchers (factors.hip /
-// solver.hip / ...), host helpers, the schedules and the handle (vb_handle_s).  api.hip: the numeric
-// phases and the LM controller; symbolic.hip: vb_finalize's host-only analysis (ordering, tile pattern,
-// Schur work lists, factorization schedules; symbolic.hpp); finalize.hip: its upload into the handle;
-// covariances.hip; multi.hip: the multi-process building blocks; tools.hip.  devmem.hpp: the owner of every
-// device buffer, pinned buffer, event and stream (the handle's lifetime groups, the per-call scratch).
+// solver.hip / ...), host helpers, the schedules and the handle.  vb_handle_s is a few groups, one per lifetime:
+// a group's owner (devmem.hpp), the device pointers into its memory and its host-side data are one object, and
+// dropping the object is the only way to undo the group.  Finalized and the lazy groups are built beside the
+// handle and installed once whole, so a failure leaves the handle as it was.  api.hip: the C-ABI and the queued
+// phases; factor_host.hip, pcg_host.hip: the drivers; symbolic.hip + finalize.hip: vb_finalize; multi.hip.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -157,7 +157,7 @@ struct Sched : SchedShape {
   int32_t *potrfTileD = nullptr, *potrfColD = nullptr, *trsmDiagD = nullptr, *trsmTargetD = nullptr,
           *trsmColD = nullptr, *updD = nullptr, *fanPairsD = nullptr, *trsmRowD = nullptr;
   int32_t *tasksFD = nullptr, *tasksBD = nullptr, *expFD = nullptr, *expBD = nullptr, *preReadyD = nullptr;
-  hipGraphExec_t graph[2] = {nullptr, nullptr};  // per tile store (vb_handle_s::tileSet)
+  hipGraphExec_t graph[2] = {nullptr, nullptr};  // per tile store (Finalized::tileSet)
 };
 
 // Two-column supernodes (VIBA_SUPERNODE, single handle): where column J + 1 is J's parent in the
@@ -182,6 +182,175 @@ struct SnSched : SnSchedShape {
   hipGraphExec_t graph[2] = {nullptr, nullptr};
 };
 
+// ---------------------------------------------------------------- the handle's groups
+// what the caller sets before vb_finalize (vb_finalize only reads it)
+struct Problem {
+  std::vector<double> data[9];
+  std::vector<uint8_t> cst[9];
+  std::vector<int32_t> fvars[14], fint[14];
+  std::vector<double> fconst[14];
+  int32_t nRS = 0;
+  std::vector<int64_t> rsOff;  // of the given tables (vb_set_rs_tables); Finalized::rsOff: the device tables'
+  std::vector<double> rsS, rsI, rsG;
+  // device rebuild of the tables (vb_set_imu_measurements / vb_set_rs_rigs)
+  std::vector<int64_t> imuT, rsMid, rsHalf;
+  std::vector<double> imuV;
+  std::vector<int32_t> rsCalib;
+  int32_t rsGravVar = -1;
+  bool rsDevice = false;
+  // --recompute-preint (vb_set_imu_stream / vb_set_imu_noise / vb_set_preint_sources): IMU streams
+  // 1.. (stream 0 is imuT / imuV), per IMU sample variances, per inertial row its IMU and interval
+  std::vector<std::vector<int64_t>> piT;
+  std::vector<std::vector<double>> piV;
+  std::vector<double> piNoise;  // 6 per IMU: accel var 3, gyro var 3, as given (Finalized::piNoise: every IMU's)
+  std::vector<PreintSrc> piSrc;
+  bool recomputePreint = false;
+  // the landmark shard and the partition as requested (Finalized::shard: the shard as resolved)
+  int64_t lmBegin = 0, lmEnd = -1;
+  bool sharded = false, isRoot = true, partSet = false;
+  int partRank = 0, partWorld = 1;  // world 1 with partSet: one rank factors its subtree and the ROOT
+};
+
+// vb_create's streams and events, destroyed last
+struct Streams {
+  DevOwner mem;
+  // st2: the small (non-visual) factor kernels -- few waves, latency-bound -- beside the visual kernels, forked
+  // after the buffer resets and joined before their first consumer.  stZ: vb_linearize's clear of the reduced
+  // system, so the small factors' evaluation (st2) does not queue behind the 2.2 GB memset (evZero).  The
+  // supernode schedule's streams (VIBA_SN_STREAMS, 1..4) are st, st2, stZ, stF, forked and launched eagerly:
+  // captured into a graph the forked schedule ran 12% slower per iteration (r05k)
+  hipStream_t st = nullptr, st2 = nullptr, stZ = nullptr, stF = nullptr;
+  hipEvent_t ev[12];
+  hipEvent_t evFork = nullptr, evJoin = nullptr;
+  hipEvent_t evZero = nullptr, evSmallE = nullptr, evZJoin = nullptr;
+  hipEvent_t evSnFork = nullptr, evSnLvl[4] = {}, evClr = nullptr, evClrDone = nullptr, evInvAt[4] = {}, evInvDone = nullptr;
+  hipEvent_t evStep = nullptr, evRs = nullptr;  // vb_optimize: box-plus done; the speculative rebuild on stF done
+};
+
+// what vb_create reads from the environment or the device, and what vb_set_solver sets
+struct Tuning {
+  bool useGraphs = true;  // the tile factorization's launches as one HIP graph per schedule and tile store
+  bool specEarly = true;  // specEarly beside the cost pass (VIBA_SPEC_EARLY=0: inside the speculative linearization)
+  bool costFuse = true;  // the global-shutter cost pass inside the speculative linearization (VIBA_COST_FUSE=0)
+  // vb_optimize: the clear of the spare tile store for the next iteration's speculative linearization
+  // queued on stZ from inside the factorization, at the top separators' chain (one stream, a few
+  // latency-bound launches per level, HBM idle) instead of beside the cost pass (VIBA_CLEAR_IN_FACTOR=0)
+  bool clearInFactor = true;
+  bool specFailDebug = false;  // VIBA_DEBUG_SPEC_FAIL=1: specPrepare fails after its first allocations (test)
+  bool useSn = true;           // VIBA_SUPERNODE=0 at creation: the column schedule
+  int snStreams = 2, numCUs = 256;
+  int64_t ptFuseMax = 256;  // levels with at most this many off-diagonal tiles run potrf + trsm in one launch
+  // vb_set_solver: direct, or S x = rhsWork by PCG over the unfactored tiles (pcg_host.hip)
+  int solverType = VB_SOLVER_DIRECT, pcgMaxIt = 40;  // Optimizer.h:43-45 defaults
+  double pcgTol = 1e-10;
+};
+
+// what changes from call to call
+struct RunState {
+  bool linearized = false, factored = false;
+  vb_phase_times times{};
+  // vb_set_deferred: the phase functions of the multi-process controllers queue their work and return
+  // without a host wait or scalar read; their scalars stay in red[0, 17) / err for one vb_read_scalars
+  bool deferred = false;
+  bool scalarsMarked = false;  // vb_mark_scalars recorded evCost since the last read
+  int specSet = 0;             // vb_spec_linearize's event set
+  int specCommitted = -1;      // the event set of the speculative linearization last committed
+  bool specPending = false;    // a vb_spec_linearize awaits vb_spec_commit
+  int32_t lastWords[2] = {0, 0};  // error words of the last check (vb_error_words)
+  bool rsTimed = false;
+  // clearWanted: factorSeqSn queues the spare store's clear (Tuning::clearInFactor; then sets clearQueued)
+  bool clearWanted = false, clearQueued = false, clearOnF = false;
+  bool factorOnly = false;  // no solve follows (vb_compute_covariances): no fused forward solve, eager
+  double pointCovMs[3] = {0.0, 0.0, 0.0};  // host ms of the last point covariances: prologue, inversion, rest
+  double calibEvalMs = 0.0;  // device time of the last vb_calib_projection_offsets' kernels (calib_eval.hip)
+  int32_t pcgIters = 0;
+  double pcgRelRes = 0.0;
+  int faultNegModelRedIt = -1, faultFailIt = -1;  // vb_debug_negate_model_reduction / _fail_iteration (tests)
+};
+
+// everything vb_finalize makes (doFinalize, finalize.hip); the handle is finalized when it has one
+struct Finalized {
+  DevOwner mem;
+  Dev d;
+  PreintArgs pi;
+  // tile-Cholesky schedules: sch[0] the whole factorization (or, partitioned, this rank's subtree
+  // plus its partial fan-in into the ROOT targets), sch[1] the ROOT separators (partitioned, rank 0);
+  // sn[]: their two-column supernode schedules (direct factorization)
+  Sched sch[2];
+  SnSched sn[2];
+  int tileSet = 0;  // which of the two tile stores d.tiles is (selects the factorization graph)
+  int64_t* padRowsD = nullptr;  // reduced rows that belong to no variable (tile alignment of parts)
+  // tiles the linearization clears (single handle): every tile but those one Schur item stores whole
+  int32_t *clearTilesD = nullptr, *shardTilesD = nullptr;
+  double* shardPack = nullptr;  // packed copy of shardTiles (vb_pack_shard_tiles)
+  double *dinv = nullptr, *yvec = nullptr, *rhsWork = nullptr, *linv = nullptr;
+  double* lscr = nullptr;    // L_JJ of the fused levels' columns (nT tiles), copied back after the factorization
+  double* lscrSn = nullptr;  // the supernode schedule's: L11 / L22 at [J] / [J + 1], L21 at [nT + J]
+  int32_t *colTilesD = nullptr, *colRowsD = nullptr, *rowTilesD = nullptr, *rowColD = nullptr;
+  int64_t *colStartD = nullptr, *rowStartD = nullptr;
+  unsigned* solveFlags = nullptr;
+  // partitioned: tiles of ROOT columns, ROOT tile rows, the row blocks this rank solves (vb_share_x)
+  int32_t *rootTilesD = nullptr, *rootRowsD = nullptr, *ownRowsD = nullptr;
+  double *rootPack = nullptr, *rowPack = nullptr, *ownPack = nullptr;
+  // host-side results of the analysis (symbolic.hpp), moved out of it
+  Layout lay;
+  Shard shard;  // the shard as resolved: lmBegin, lmEnd, isRoot
+  PartitionSets part;
+  std::vector<int32_t> lmOfPoint;
+  std::vector<int64_t> colStart, rowStart;  // per tile column into colTilesH / colRowsH, per tile row into rowColH
+  std::vector<int32_t> colTilesH, colRowsH, rowColH;
+  std::vector<uint8_t> tileFill;     // per tile: 1 = created by the symbolic factorization (zero in S)
+  std::vector<int32_t> shardTiles;   // exact tiles of this (non-root) shard's partial system
+  std::vector<int32_t> visRowOfPos;  // the visual factor row (vb_add_factors order) at every position of obCostOrder
+  std::vector<int64_t> rsOff;        // offsets of the device rolling-shutter tables (capacities when rebuilt there)
+  std::vector<double> piNoise;       // 6 per IMU, every IMU of the preintegration sources (device copy: pi.noise)
+  int64_t nParams = 0, order = 0, nClear = 0, nTileEnt = 0, tileFirst = 0, tileCount = 0, nPairs = 0;
+  int32_t nLevels = 0;
+  int64_t costRsB[2] = {0, 0};  // obCostOrder: where the rolling-shutter observations of [obB, obE), [fB, fE) start
+  ~Finalized() {
+    for (hipGraphExec_t g : {sn[0].graph[0], sn[0].graph[1], sn[1].graph[0], sn[1].graph[1], sch[0].graph[0],
+                             sch[0].graph[1], sch[1].graph[0], sch[1].graph[1]})
+      if (g) hipGraphExecDestroy(g);
+  }
+};
+
+// vb_optimize's speculative linearization (specEnqueue): the next iteration's rolling-shutter rebuild
+// and linearization are queued behind this iteration's cost pass, before the host reads its scalars,
+// into a second tile store, ResultCache, gradient and rolling-shutter table set (and reduction /
+// error slots red[48, 64), err[4, 6)); they are swapped in when the step is accepted at full size
+// (specCommit), and left unused otherwise (the host then takes the step-rescaling path, which needs
+// this iteration's factor, cache and tables as they are).  Dropped only when its own preparation fails, or with
+// the handle -- never after a specCommit: the pointers it swaps with Finalized::d need both owners to the end.
+struct SpecState {
+  DevOwner mem;
+  double *tilesAlt = nullptr, *cacheAlt = nullptr, *gRedAlt = nullptr;
+  double *rsSAlt = nullptr, *rsIAlt = nullptr, *rsGAlt = nullptr;
+  int32_t* rsNAlt = nullptr;
+  hipStream_t stR = nullptr;  // the scalar readback, beside the speculative work
+  hipEvent_t evCost = nullptr, evS[2][4] = {};
+  double* hostRed = nullptr;  // pinned readback buffer: red[0, 17), then err[0, 2) as int32
+};
+
+// the PCG path's buffers (pcgPrepare): made at its first use, grown at a preconditioner type's first use
+struct PcgState {
+  DevOwner mem;
+  int32_t *symvTilesD = nullptr, *symvRCD = nullptr;  // the tiles of S (no fill) and their (row, column)
+  int64_t nSymv = 0;
+  double *pcgR = nullptr, *pcgZ = nullptr, *pcgP = nullptr, *pcgAp = nullptr, *pcgB = nullptr;
+  double *jacL = nullptr, *tilesGS = nullptr;  // Jacobi block factors / Gauss-Seidel pseudo-factor
+  // LowerPrecSolvePrecond (lowprec.hip): fp32 factor tiles, fp32 diagonal-tile inverses, fp32 vector
+  float *lpTiles = nullptr, *lpLinv = nullptr, *lpT = nullptr;
+};
+
+// point refinement groups (built at the first vb_refine_points): observations by point
+struct RefineState {
+  DevOwner mem;
+  int64_t nRefG = 0;
+  int64_t* refStartD = nullptr;
+  int32_t *refObsD = nullptr, *refPtD = nullptr;
+  double *refBackD = nullptr, *refAccD = nullptr;
+};
+
 // the residual report's device state (report.hip), made at its first call
 struct ReportState {
   DevOwner mem;
@@ -191,183 +360,32 @@ struct ReportState {
   double histMs = 0.0;  // device time of the last vb_error_histogram's kernels
 };
 
-struct vb_handle_s {
-  vb_config cfg;
-  // what the handle took from the HIP runtime, one owner per lifetime (devmem.hpp): a group is dropped as a
-  // unit, all of them with the handle, in reverse order (the streams of `create` last)
-  DevOwner create;  // vb_create: streams and events
-  DevOwner fin;     // everything doFinalize makes
-  DevOwner spec;    // specPrepare
-  DevOwner pcg;     // pcgPrepare: the PCG vectors and the preconditioners' stores
-  DevOwner refine;  // vb_refine_points
-  DevOwner prof;    // profEv
-  hipStream_t st = nullptr;
-  std::vector<double> data[9];
-  std::vector<uint8_t> cst[9];
-  std::vector<int32_t> fvars[14], fint[14];
-  std::vector<double> fconst[14];
-  int32_t nRS = 0;
-  std::vector<int64_t> rsOff;
-  std::vector<double> rsS, rsI, rsG;
-  // device rebuild of the tables (vb_set_imu_measurements / vb_set_rs_rigs)
-  std::vector<int64_t> imuT, rsMid, rsHalf;
-  std::vector<double> imuV;
-  std::vector<int32_t> rsCalib;
-  int32_t rsGravVar = -1;
-  bool rsDevice = false, rsTimed = false;
-  // --recompute-preint (vb_set_imu_stream / vb_set_imu_noise / vb_set_preint_sources): IMU streams
-  // 1.. (stream 0 is imuT / imuV), per IMU sample variances, per inertial row its IMU and interval
-  std::vector<std::vector<int64_t>> piT;
-  std::vector<std::vector<double>> piV;
-  std::vector<double> piNoise;  // 6 per IMU: accel var 3, gyro var 3
-  std::vector<PreintSrc> piSrc;
-  PreintArgs pi;
-  bool recomputePreint = false;
-  // point refinement groups (built at the first vb_refine_points): observations by point
-  int64_t nRefG = 0;
-  int64_t* refStartD = nullptr;
-  int32_t *refObsD = nullptr, *refPtD = nullptr;
-  double *refBackD = nullptr, *refAccD = nullptr;
-  // residual report (report.hip): the visual factor row (vb_add_factors order) at every position of
-  // obCostOrder, and the report's device state
-  std::vector<int32_t> visRowOfPos;
-  ReportState rep;
-  double calibEvalMs = 0.0;  // device time of the last vb_calib_projection_offsets' kernels (calib_eval.hip)
-  bool finalized = false;
-  Dev d;
-  // symbolic (host)
-  std::vector<int32_t> rvKind, rvHandle, rvDim;
-  std::vector<int64_t> rvOff;
-  std::vector<int32_t> lmOfPoint;
-  int64_t nParams = 0, order = 0, nLmObs = 0, nLmEnt = 0, nObEnt = 0, nRedReal = 0, nParts = 0, nPadRows = 0;
-  int64_t* padRowsD = nullptr;  // reduced rows that belong to no variable (tile alignment of parts)
-  std::vector<int64_t> colStart;   // per tile column into colTilesH / colRowsH
-  std::vector<uint8_t> tileFill;   // per tile: 1 = created by the symbolic factorization (zero in S)
-  std::vector<int32_t> colTilesH, colRowsH;
-  // tile-Cholesky schedules: sch[0] the whole factorization (or, partitioned, this rank's subtree
-  // plus its partial fan-in into the ROOT targets), sch[1] the ROOT separators (partitioned, rank 0)
-  Sched sch[2];
-  int32_t nLevels = 0;
-  int64_t nPairs = 0;
-  std::vector<int32_t> rootTiles, rootRows;  // partitioned: tiles of ROOT columns, ROOT tile rows
-  int32_t *rootTilesD = nullptr, *rootRowsD = nullptr;
-  double *rootPack = nullptr, *rowPack = nullptr;
-  int32_t* ownRowsD = nullptr;  // row blocks this rank solves (vb_share_x)
-  int64_t nOwnRows = 0;
-  double* ownPack = nullptr;
-  std::vector<int64_t> rowStart;   // per tile row into rowTilesH / rowColH
-  std::vector<int32_t> rowTilesH, rowColH;
-  int32_t *colTilesD = nullptr, *colRowsD = nullptr, *rowTilesD = nullptr,
-          *rowColD = nullptr;
-  int64_t *colStartD = nullptr, *rowStartD = nullptr;
-  unsigned* solveFlags = nullptr;
-  int numCUs = 256;
-  double *dinv = nullptr, *yvec = nullptr, *rhsWork = nullptr, *linv = nullptr;
-  // a factorization without a solve to follow (vb_compute_covariances): no fused forward solve, eager
-  bool factorOnly = false;
-  // host time [ms] of the last vb_compute_point_covariances: prologue, selected inversion, the rest
-  double pointCovMs[3] = {0.0, 0.0, 0.0};
-  // tiles the linearization clears (single handle): every tile but those one Schur item stores whole
-  int32_t* clearTilesD = nullptr;
-  int64_t nClear = 0;
-  // shard
-  int64_t lmBegin = 0, lmEnd = -1;
-  bool sharded = false;  // vb_set_landmark_shard called
-  bool isRoot = true;
-  int partRank = 0, partWorld = 1;  // vb_set_partition (partitioned factorization), else 1
-  int32_t lastWords[2] = {0, 0};   // error words of the last check (vb_error_words)
-  bool partSet = false;             // vb_set_partition called (world 1: one rank factors its subtree and the ROOT)
-  std::vector<int8_t> colOwner;     // per tile column: owning rank, partWorld = ROOT (rank 0)
-  std::vector<std::pair<int64_t, int64_t>> zeroRuns;  // partitioned: tile runs this rank writes (its + ROOT columns)
-  int64_t tileFirst = 0, tileCount = 0, nTileEnt = 0;
-  std::vector<int32_t> shardTiles;  // exact tiles of this (non-root) shard's partial system
-  int32_t* shardTilesD = nullptr;
-  double* shardPack = nullptr;      // packed copy of those tiles (vb_pack_shard_tiles)
-  // iterative reduced solve (vb_set_solver; pcg.hip): S x = rhsWork by PCG over the unfactored tiles
-  int solverType = VB_SOLVER_DIRECT, pcgMaxIt = 40;  // Optimizer.h:43-45 defaults
-  int faultNegModelRedIt = -1;  // vb_debug_negate_model_reduction (test fault injection)
-  int faultFailIt = -1;         // vb_debug_fail_iteration (test fault injection)
-  double pcgTol = 1e-10;
-  int32_t pcgIters = 0;
-  double pcgRelRes = 0.0;
-  int32_t *symvTilesD = nullptr, *symvRCD = nullptr;  // the tiles of S (no fill) and their (row, column)
-  int64_t nSymv = 0;
-  double *pcgR = nullptr, *pcgZ = nullptr, *pcgP = nullptr, *pcgAp = nullptr, *pcgB = nullptr;
-  double *jacL = nullptr, *tilesGS = nullptr;  // Jacobi block factors / Gauss-Seidel pseudo-factor
-  // LowerPrecSolvePrecond (lowprec.hip): fp32 factor tiles, fp32 diagonal-tile inverses, fp32 vector
-  float *lpTiles = nullptr, *lpLinv = nullptr, *lpT = nullptr;
-  // the tile factorization's launches, captured into a HIP graph per schedule and tile store
-  // (VIBA_NO_GRAPHS=1: eager)
-  bool useGraphs = true;
-  bool specEarly = true;  // specEarly beside the cost pass (VIBA_SPEC_EARLY=0: inside the speculative linearization)
-  // vb_optimize folds the cost pass of the global-shutter observations into the speculative
-  // linearization (VIBA_COST_FUSE=0: the whole cost pass first); costRsB: where the rolling-shutter
-  // observations of [obB, obE) and [fB, fE) start in obCostOrder (each range global shutter first)
-  bool costFuse = true;
-  // vb_optimize: the clear of the spare tile store for the next iteration's speculative linearization
-  // queued on stZ from inside the factorization, at the top separators' chain (one stream, a few
-  // latency-bound launches per level, HBM idle) instead of beside the cost pass (VIBA_CLEAR_IN_FACTOR=0);
-  // clearWanted: factorSeqSn queues it (then sets clearQueued)
-  bool clearInFactor = true, clearWanted = false, clearQueued = false, clearOnF = false;
-  int64_t costRsB[2] = {0, 0};
-  // vb_optimize's speculative linearization (specEnqueue): the next iteration's rolling-shutter rebuild
-  // and linearization are queued behind this iteration's cost pass, before the host reads its scalars,
-  // into a second tile store, ResultCache, gradient and rolling-shutter table set (and reduction /
-  // error slots red[48, 64), err[4, 6)); they are swapped in when the step is accepted at full size
-  // (specCommit), and left unused otherwise (the host then takes the step-rescaling path, which needs
-  // this iteration's factor, cache and tables as they are)
-  double *tilesAlt = nullptr, *cacheAlt = nullptr, *gRedAlt = nullptr;
-  double *rsSAlt = nullptr, *rsIAlt = nullptr, *rsGAlt = nullptr;
-  int32_t* rsNAlt = nullptr;
-  int tileSet = 0;            // which of the two tile stores d.tiles is (selects the factorization graph)
-  hipStream_t stR = nullptr;  // the scalar readback, beside the speculative work
-  hipEvent_t evCost = nullptr, evS[2][4] = {};
-  double* hostRed = nullptr;  // pinned readback buffer: red[0, 17), then err[0, 2) as int32
-  size_t profAtCost = 0;      // profiled event pairs recorded before evCost
-  bool specReady = false;     // every speculative buffer, event and stream above exists (specPrepare)
-  SnSched sn[2];              // two-column supernode schedules of sch[0] / sch[1] (direct factorization)
-  bool useSn = true;          // VIBA_SUPERNODE=0 at creation: the column schedule
-  // streams of the single-handle supernode schedule (VIBA_SN_STREAMS, 1..4): 1, 2, 3 are st2, stZ, stF
-  // (idle during the factorization); fork and per-level events.  The forked schedule is launched eagerly:
-  // captured into a graph it ran 12% slower per iteration (r05k)
-  int snStreams = 2;
-  hipStream_t stF = nullptr;
-  hipEvent_t evSnFork = nullptr, evSnLvl[4] = {}, evClr = nullptr, evClrDone = nullptr, evInvAt[4] = {}, evInvDone = nullptr;
-  hipEvent_t evStep = nullptr, evRs = nullptr;  // vb_optimize: box-plus done; the speculative rebuild on stF done
-  // vb_set_deferred: the phase functions of the multi-process controllers queue their work and return
-  // without a host wait or scalar read; their scalars stay in red[0, 17) / err for one vb_read_scalars
-  bool deferred = false;
-  bool scalarsMarked = false;  // vb_mark_scalars recorded evCost since the last read
-  int specSet = 0;             // vb_spec_linearize's event set
-  int specCommitted = -1;      // the event set of the speculative linearization last committed
-  bool specPending = false;    // a vb_spec_linearize awaits vb_spec_commit
-  bool specFailDebug = false; // VIBA_DEBUG_SPEC_FAIL=1 at creation: specPrepare fails after its first
-                              // allocations (test of the release + plain-controller fallback)
-  // state
-  bool linearized = false, factored = false;
-  vb_phase_times times{};
-  hipEvent_t ev[12];
-  // side stream: the small (non-visual) factor kernels -- few waves, latency-bound -- run beside
-  // the visual kernels, forked after the buffer resets and joined before their first consumer
-  hipStream_t st2 = nullptr;
-  hipEvent_t evFork = nullptr, evJoin = nullptr;
-  // vb_linearize: the reduced system's clear on a stream of its own (stZ), so the small factors'
-  // evaluation (st2) does not queue behind the 2.2 GB memset; their assembly waits for it (evZero)
-  hipStream_t stZ = nullptr;
-  hipEvent_t evZero = nullptr, evSmallE = nullptr, evZJoin = nullptr;
-  int64_t ptFuseMax = 256;  // levels with at most this many off-diagonal tiles run potrf + trsm in one launch
-  double* lscr = nullptr;   // L_JJ of the fused levels' columns (nT tiles), copied back after the factorization
-  double* lscrSn = nullptr; // the supernode schedule's: L11 / L22 at [J] / [J + 1], L21 at [nT + J]
-  // per-kernel-family device timing (vb_profile_kernel): event pairs around every launch
-  int profFamily = -1;
-  std::vector<hipEvent_t> profEv;
-  size_t profUsed = 0;
-  size_t profDone = 0;  // leading profEv entries known complete, harvested after the next enqueue
-  int64_t profLaunches = 0;
-  double profMs = 0.0;
-  double profBusyMs = 0.0;  // union of the profiled launches' intervals
+// per-kernel-family device timing (vb_profile_kernel): event pairs around every launch
+struct ProfState {
+  DevOwner mem;
+  int family = -1;
+  std::vector<hipEvent_t> ev;
+  size_t used = 0;
+  size_t done = 0;    // leading ev entries known complete, harvested after the next enqueue
+  size_t atCost = 0;  // profiled event pairs recorded before evCost
+  int64_t launches = 0;
+  double ms = 0.0, busyMs = 0.0;  // summed launch durations; the union of the launches' intervals
 };
 
+// destroyed in reverse order: the lazy groups, then `fin`, the streams last
+struct vb_handle_s {
+  vb_config cfg;
+  Streams str;
+  Problem prob;
+  Tuning tune;
+  RunState run;
+  std::unique_ptr<Finalized> fin;
+  std::unique_ptr<SpecState> spec;
+  std::unique_ptr<PcgState> pcg;
+  std::unique_ptr<RefineState> refine;
+  std::unique_ptr<ReportState> rep;
+  ProfState prof;
+};
 
 // ---------------------------------------------------------------- shared host functions
 #include "host_decl.hpp"

@@ -1,8 +1,28 @@
-// Declarations of the host functions the engine's translation units share (host.hpp): api.hip defines
-// all but doFinalize (finalize.hip) and vb_optimize's speculation (optimize.hip).
+// Declarations of the host functions the engine's translation units share (host.hpp), each group under the
+// file that defines it.
 #pragma once
 
 namespace viba_host {
+// kernel families for vb_profile_kernel
+enum { KF_VISUAL_LIN = 0, KF_LANDMARK, KF_SCHUR, KF_POTRF, KF_GEMM, KF_FWD, KF_BWD, KF_BACKSUB, KF_VISUAL_COST,
+       KF_SMALL, KF_TRSM, KF_SYMV, KF_COUNT };
+
+inline void profBegin(vb_handle h, int fam) {
+  if (h->prof.family != fam) return;
+  if (h->prof.used + 2 > h->prof.ev.size()) {
+    for (int i = 0; i < 256; i++) {
+      hipEvent_t e;
+      (void)h->prof.mem.event(&e);
+      h->prof.ev.push_back(e);
+    }
+  }
+  g_prof.start = h->prof.ev[h->prof.used], g_prof.stop = h->prof.ev[h->prof.used + 1], g_prof.consumed = false;
+}
+inline void profEnd(vb_handle h, int fam) {
+  if (h->prof.family != fam) return;
+  if (g_prof.consumed) h->prof.used += 2;  // the wrapper launched the family's kernel with the events
+  g_prof = ProfSlot();
+}
 // kernel-family event timing and error words (api.hip)
 float profPairMs(hipEvent_t a, hipEvent_t b);
 double elapsed(hipEvent_t a, hipEvent_t b);
@@ -14,15 +34,22 @@ int readRed(vb_handle h, double* out, int i0, int n);
 int readRedErr(vb_handle h, double* out, int n);
 // numeric phases (api.hip)
 bool smallHere(vb_handle h, int mode);
+// the factorization and solve drivers (factor_host.hip)
+bool fwdFused(vb_handle h);
 int factorReduced(vb_handle h, int which = 0);
 int solveReduced(vb_handle h, int which = 0, int phases = 3);
 void backSubstitute(vb_handle h, int which);
+// the iterative reduced solve (pcg_host.hip)
+bool pcgMode(vb_handle h);
+int precondInit(vb_handle h);
+int pcgSolve(vb_handle h);
 // vb_finalize (finalize.hip)
 int doFinalize(vb_handle h);
 // is the whole problem on this handle (no landmark shard, no partition)?  vb_refine_points alone accepts a
 // vb_set_landmark_shard call that names every landmark on the root (shardCall = false)
 inline bool wholeProblem(vb_handle h, bool shardCall = true) {
-  return !(h->partSet || (shardCall && h->sharded) || h->d.lmB != 0 || h->d.lmE != h->d.nPts || !h->isRoot);
+  const Dev& d = h->fin->d;
+  return !(h->prob.partSet || (shardCall && h->prob.sharded) || d.lmB != 0 || d.lmE != d.nPts || !h->fin->shard.isRoot);
 }
 // capacity of a rolling-shutter table that is rebuilt on the device: the IMU samples (stamps t[0, n) [ns]) of
 // [mid - half, mid + half] [us] widened by 20 ms on both sides (the reference-time offsets of the calibration

@@ -6,43 +6,39 @@
 #include "lm_controller.hpp"
 
 extern "C" {
-// ---- vb_optimize's speculative linearization of the next iteration (vb_handle_s::tilesAlt ..)
+// ---- vb_optimize's speculative linearization of the next iteration (SpecState, host.hpp)
 // The spare tile store (nTiles x 32 KB: 2.2 GB at config C), ResultCache, gradient and rolling-shutter
 // tables of the speculative linearization, allocated at the first vb_optimize that speculates.  Returns
 // false when any of it cannot be had: the caller then runs the plain controller (no speculation), as
 // before the speculative path existed, instead of failing a problem that fits without it.
 bool specPrepare(vb_handle h) {
-  if (h->specReady) return true;
-  Dev& d = h->d;
-  DevOwner& m = h->spec;
-  bool ok = !m.zeroed(&h->tilesAlt, (size_t)d.nTiles * TS * TS) && !m.zeroed(&h->cacheAlt, d.nObs) &&
-            !m.zeroed(&h->gRedAlt, (size_t)d.nT * TS) && !h->specFailDebug;
-  if (ok && h->rsDevice) {
-    const int64_t ns = h->rsOff[h->nRS];
-    ok = !m.zeroed(&h->rsSAlt, ns * 11) && !m.zeroed(&h->rsIAlt, (ns - h->nRS) * 9) &&
-         !m.zeroed(&h->rsGAlt, (size_t)h->nRS * 3) && !m.zeroed(&h->rsNAlt, h->nRS);
+  if (h->spec) return true;
+  const Dev& d = h->fin->d;
+  auto s = std::make_unique<SpecState>();
+  DevOwner& m = s->mem;
+  bool ok = !m.zeroed(&s->tilesAlt, (size_t)d.nTiles * TS * TS) && !m.zeroed(&s->cacheAlt, d.nObs) &&
+            !m.zeroed(&s->gRedAlt, (size_t)d.nT * TS) && !h->tune.specFailDebug;
+  if (ok && h->prob.rsDevice) {
+    const int64_t nRS = h->prob.nRS, ns = h->fin->rsOff[nRS];
+    ok = !m.zeroed(&s->rsSAlt, ns * 11) && !m.zeroed(&s->rsIAlt, (ns - nRS) * 9) && !m.zeroed(&s->rsGAlt, (size_t)nRS * 3) &&
+         !m.zeroed(&s->rsNAlt, nRS);
   }
-  for (auto& row : h->evS)
+  for (auto& row : s->evS)
     for (hipEvent_t& e : row) ok = ok && !m.event(&e);
-  ok = ok && !m.event(&h->evCost, hipEventDisableTiming) && !m.stream(&h->stR) && !m.pinned(&h->hostRed, 32);
-  if (!ok) {  // give back what was had before the failure (nothing has been swapped into h->d then)
-    m.release();
-    h->tilesAlt = h->cacheAlt = h->gRedAlt = h->rsSAlt = h->rsIAlt = h->rsGAlt = h->hostRed = nullptr;
-    h->rsNAlt = nullptr, h->evCost = nullptr, h->stR = nullptr;
-    for (auto& row : h->evS)
-      for (hipEvent_t& e : row) e = nullptr;
-    (void)hipGetLastError();
-  }
-  h->specReady = ok;
+  ok = ok && !m.event(&s->evCost, hipEventDisableTiming) && !m.stream(&s->stR) && !m.pinned(&s->hostRed, 32);
+  // a failure gives back what was had before it, with s (nothing has been swapped into Finalized::d then);
+  // once installed the group stays to the handle's end (SpecState, host.hpp)
+  if (ok) h->spec = std::move(s);
+  else (void)hipGetLastError();
   return ok;
 }
-// the buffers the speculative work writes instead of h->d's
+// the buffers the speculative work writes instead of Finalized::d's
 Dev specDev(vb_handle h) {
-  Dev ds = h->d;
-  ds.tiles = h->tilesAlt, ds.cacheW = h->cacheAlt, ds.gRed = h->gRedAlt;
-  ds.red = h->d.red + 48, ds.err = h->d.err + 4;
-  ds.redS = h->d.redS + 64 * 8;  // own stripes: the fused cost pass adds into the handle's (costS)
-  if (h->rsDevice) ds.rsS = h->rsSAlt, ds.rsI = h->rsIAlt, ds.rsG = h->rsGAlt, ds.rsN = h->rsNAlt;
+  Dev ds = h->fin->d;
+  ds.tiles = h->spec->tilesAlt, ds.cacheW = h->spec->cacheAlt, ds.gRed = h->spec->gRedAlt;
+  ds.red = h->fin->d.red + 48, ds.err = h->fin->d.err + 4;
+  ds.redS = h->fin->d.redS + 64 * 8;  // own stripes: the fused cost pass adds into the handle's (costS)
+  if (h->prob.rsDevice) ds.rsS = h->spec->rsSAlt, ds.rsI = h->spec->rsIAlt, ds.rsG = h->spec->rsGAlt, ds.rsN = h->spec->rsNAlt;
   return ds;
 }
 // ark_vi_ba's preStepCallback (the rolling-shutter rebuild at the accepted variables) and the
@@ -52,19 +48,19 @@ Dev specDev(vb_handle h) {
 // the cost pass; the main stream only waits for it.
 int specEnqueue(vb_handle h, int dontRetry, int p, bool early, bool rsDone, bool fuseCost) {
   Dev ds = specDev(h);
-  if (fuseCost) ds.costS = h->d.redS;
+  if (fuseCost) ds.costS = h->fin->d.redS;
   if (!early && !rsDone) {
-    HIPCHK(hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->st));
-    HIPCHK(hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->st));
+    HIPCHK(hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->str.st));
+    HIPCHK(hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->str.st));
   }
   if (rsDone) {
-    HIPCHK(hipStreamWaitEvent(h->st, h->evRs, 0));
+    HIPCHK(hipStreamWaitEvent(h->str.st, h->str.evRs, 0));
   } else {
-    HIPCHK(hipEventRecord(h->evS[p][0], h->st));
-    if (h->rsDevice) launch_rs_build(ds, h->st);
-    HIPCHK(hipEventRecord(h->evS[p][1], h->st));
+    HIPCHK(hipEventRecord(h->spec->evS[p][0], h->str.st));
+    if (h->prob.rsDevice) launch_rs_build(ds, h->str.st);
+    HIPCHK(hipEventRecord(h->spec->evS[p][1], h->str.st));
   }
-  return linearizeBody(h, ds, 1, dontRetry, h->evS[p][2], h->evS[p][3], early);
+  return linearizeBody(h, ds, 1, dontRetry, h->spec->evS[p][2], h->spec->evS[p][3], early);
 }
 // The part of the speculative linearization that needs only the stepped variables, queued on stZ after
 // the box-plus so it runs beside the cost pass (which leaves the HBM and most CUs idle): the small
@@ -75,41 +71,41 @@ int specEarly(vb_handle h, bool cleared, bool storeCleared) {
   if (!smallHere(h, 0)) return 0;
   const Dev ds = specDev(h);
   if (!cleared) {
-    HIPCHK(hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->st));
-    HIPCHK(hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->st));
+    HIPCHK(hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->str.st));
+    HIPCHK(hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->str.st));
   }
-  HIPCHK(hipEventRecord(h->evFork, h->st));
-  HIPCHK(hipStreamWaitEvent(h->stZ, h->evFork, 0));
-  if (storeCleared && h->clearOnF) HIPCHK(hipStreamWaitEvent(h->stZ, h->evClrDone, 0));
-  launch_small_eval(ds, 0, ds.gRed, h->stZ);
+  HIPCHK(hipEventRecord(h->str.evFork, h->str.st));
+  HIPCHK(hipStreamWaitEvent(h->str.stZ, h->str.evFork, 0));
+  if (storeCleared && h->run.clearOnF) HIPCHK(hipStreamWaitEvent(h->str.stZ, h->str.evClrDone, 0));
+  launch_small_eval(ds, 0, ds.gRed, h->str.stZ);
   // (storeCleared: the factorization queued the clear on stZ already, factorSeqSn)
-  return storeCleared ? 0 : clearReduced(h, ds, h->stZ);
+  return storeCleared ? 0 : clearReduced(h, ds, h->str.stZ);
 }
 // the step was accepted at full size: the speculative buffers become the handle's
 void specCommit(vb_handle h) {
-  Dev& d = h->d;
-  std::swap(d.tiles, h->tilesAlt);
-  std::swap(d.cache, h->cacheAlt);
+  Dev& d = h->fin->d;
+  std::swap(d.tiles, h->spec->tilesAlt);
+  std::swap(d.cache, h->spec->cacheAlt);
   d.cacheW = d.cache;
-  std::swap(d.gRed, h->gRedAlt);
-  if (h->rsDevice) {
-    std::swap(d.rsS, h->rsSAlt), std::swap(d.rsI, h->rsIAlt);
-    std::swap(d.rsG, h->rsGAlt), std::swap(d.rsN, h->rsNAlt);
+  std::swap(d.gRed, h->spec->gRedAlt);
+  if (h->prob.rsDevice) {
+    std::swap(d.rsS, h->spec->rsSAlt), std::swap(d.rsI, h->spec->rsIAlt);
+    std::swap(d.rsG, h->spec->rsGAlt), std::swap(d.rsN, h->spec->rsNAlt);
   }
-  h->tileSet ^= 1;
-  launch_spec_commit(d, h->st);
+  h->fin->tileSet ^= 1;
+  launch_spec_commit(d, h->str.st);
 }
 // the iteration's scalars red[0, n) and error words, read on the readback stream once the cost pass
 // (evCost) is done, while whatever was queued behind it runs
 int readIterScalars(vb_handle h, double* out, int n) {
-  HIPCHK(hipStreamWaitEvent(h->stR, h->evCost, 0));
-  HIPCHK(hipMemcpyAsync(h->hostRed, h->d.red, n * sizeof(double), hipMemcpyDeviceToHost, h->stR));
-  HIPCHK(hipMemcpyAsync(h->hostRed + 24, h->d.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stR));
-  HIPCHK(hipStreamSynchronize(h->stR));
-  std::copy(h->hostRed, h->hostRed + n, out);
-  h->profDone = h->profAtCost;
+  HIPCHK(hipStreamWaitEvent(h->spec->stR, h->spec->evCost, 0));
+  HIPCHK(hipMemcpyAsync(h->spec->hostRed, h->fin->d.red, n * sizeof(double), hipMemcpyDeviceToHost, h->spec->stR));
+  HIPCHK(hipMemcpyAsync(h->spec->hostRed + 24, h->fin->d.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->spec->stR));
+  HIPCHK(hipStreamSynchronize(h->spec->stR));
+  std::copy(h->spec->hostRed, h->spec->hostRed + n, out);
+  h->prof.done = h->prof.atCost;
   int32_t ee[2];
-  std::memcpy(ee, h->hostRed + 24, sizeof(ee));
+  std::memcpy(ee, h->spec->hostRed + 24, sizeof(ee));
   return errFromWords(h, ee);
 }
 
@@ -141,7 +137,7 @@ struct OptimizeOps {
     } else {
       // ark_vi_ba's preStepCallback (main_AriaKit_ViBa.cpp:95-101): updateRollingShutterData
       // and, under --recompute-preint, the preintegrations from the IMU streams (InertialFactors.cpp:19-70)
-      if ((h->rsDevice || preint) && (rc = rsUpdateAsync(h, h->rsDevice, preint))) return rc;
+      if ((h->prob.rsDevice || preint) && (rc = rsUpdateAsync(h, h->prob.rsDevice, preint))) return rc;
       if (pre) pre(it, user);
       if ((rc = linearizeEnqueue(h, 1, dontRetry))) return rc;
     }
@@ -149,11 +145,11 @@ struct OptimizeOps {
     // reads their scalars (costs, CostStats, model reduction, step ratios) and errors once, after the cost
     // pass: none of them changes what the queued work does
     const bool specNext = speculate && it + 1 < maxIt;
-    const bool early = specNext && smallHere(h, 0) && h->specEarly;
-    h->clearWanted = early && h->clearInFactor, h->clearQueued = false;
+    const bool early = specNext && smallHere(h, 0) && h->tune.specEarly;
+    h->run.clearWanted = early && h->tune.clearInFactor, h->run.clearQueued = false;
     rc = dampFactorSolveEnqueue(h, damping, false);
-    const bool storeCleared = h->clearQueued;
-    h->clearWanted = h->clearQueued = false;
+    const bool storeCleared = h->run.clearQueued;
+    h->run.clearWanted = h->run.clearQueued = false;
     if (rc) return rc;
     if ((rc = vb_backup(h))) return rc;
     backedUp = true;
@@ -163,31 +159,31 @@ struct OptimizeOps {
     // error bits), and the main stream waits for it (evRs) before the linearization -- and so before
     // anything the host queues after its read, e.g. a restore of the variables the rebuild reads
     bool rsSide = false;
-    if (specNext && h->rsDevice) {
+    if (specNext && h->prob.rsDevice) {
       const Dev ds = specDev(h);
       const int p = specSet ^ 1;
-      if (hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->st) != hipSuccess ||
-          hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->st) != hipSuccess ||
-          hipEventRecord(h->evStep, h->st) != hipSuccess || hipStreamWaitEvent(h->stF, h->evStep, 0) != hipSuccess ||
-          hipEventRecord(h->evS[p][0], h->stF) != hipSuccess)
+      if (hipMemsetAsync(ds.red, 0, 16 * sizeof(double), h->str.st) != hipSuccess ||
+          hipMemsetAsync(ds.err, 0, 2 * sizeof(int32_t), h->str.st) != hipSuccess ||
+          hipEventRecord(h->str.evStep, h->str.st) != hipSuccess || hipStreamWaitEvent(h->str.stF, h->str.evStep, 0) != hipSuccess ||
+          hipEventRecord(h->spec->evS[p][0], h->str.stF) != hipSuccess)
         return fail(VB_E_HIP, "speculative rebuild fork");
-      launch_rs_build(ds, h->stF);
-      if (hipEventRecord(h->evS[p][1], h->stF) != hipSuccess || hipEventRecord(h->evRs, h->stF) != hipSuccess)
+      launch_rs_build(ds, h->str.stF);
+      if (hipEventRecord(h->spec->evS[p][1], h->str.stF) != hipSuccess || hipEventRecord(h->str.evRs, h->str.stF) != hipSuccess)
         return fail(VB_E_HIP, "speculative rebuild join");
       rsSide = true;
     }
     if (early && (rc = specEarly(h, rsSide, storeCleared))) return rc;
     // the global-shutter part of the cost pass inside the speculative linearization (every observation
     // evaluated there: not under dontRetry)
-    const bool fuseCost = specNext && h->costFuse && !dontRetry;
+    const bool fuseCost = specNext && h->tune.costFuse && !dontRetry;
     if ((rc = fuseCost ? costFusedEnqueue(h) : costEnqueue(h, 1, false))) return rc;
     const bool wasSpec = specQueued;
     const int wasSet = specSet;
     specQueued = false;
     if (speculate) {
       if (!fuseCost) {  // (fused: recorded after the speculative visual linearization)
-        if (hipEventRecord(h->evCost, h->st) != hipSuccess) return fail(VB_E_HIP, "hipEventRecord");
-        h->profAtCost = h->profUsed;
+        if (hipEventRecord(h->spec->evCost, h->str.st) != hipSuccess) return fail(VB_E_HIP, "hipEventRecord");
+        h->prof.atCost = h->prof.used;
       }
       // the next iteration's rebuild + linearization, assuming this step is accepted at full size
       if (specNext) {
@@ -196,28 +192,28 @@ struct OptimizeOps {
         specQueued = true;
       }
     }
-    profHarvestPrefix(h, h->profDone);  // the previous iteration's event times, read while this one runs
+    profHarvestPrefix(h, h->prof.done);  // the previous iteration's event times, read while this one runs
     double r[17];
     if ((rc = speculate ? readIterScalars(h, r, 17) : readRedErr(h, r, 17))) return rc;
-    if (it == h->faultFailIt) return fail(VB_E_NUMERIC, "reduced system Cholesky breakdown (injected)");
+    if (it == h->run.faultFailIt) return fail(VB_E_NUMERIC, "reduced system Cholesky breakdown (injected)");
     out->prev_cost = r[0], out->model_reduction = 0.5 * r[16];
-    if (it == h->faultNegModelRedIt) out->model_reduction = -out->model_reduction;  // test fault injection
-    const double n = (double)std::max<int64_t>(1, h->nParams);
+    if (it == h->run.faultNegModelRedIt) out->model_reduction = -out->model_reduction;  // test fault injection
+    const double n = (double)std::max<int64_t>(1, h->fin->nParams);
     out->step_rms_ratio = std::sqrt(r[9] / n);
     costStats(h, r + 1, &out->new_cost, &out->stats);
     if (wasSpec) {
-      h->times.linearize_ms = elapsed(h->evS[wasSet][2], h->evS[wasSet][3]);
-      if (h->rsDevice) h->times.rs_update_ms = elapsed(h->evS[wasSet][0], h->evS[wasSet][1]);
+      h->run.times.linearize_ms = elapsed(h->spec->evS[wasSet][2], h->spec->evS[wasSet][3]);
+      if (h->prob.rsDevice) h->run.times.rs_update_ms = elapsed(h->spec->evS[wasSet][0], h->spec->evS[wasSet][1]);
     } else {
-      h->times.linearize_ms = elapsed(h->ev[0], h->ev[1]);
-      if (h->rsTimed) h->times.rs_update_ms = elapsed(h->ev[8], h->ev[9]), h->rsTimed = false;
+      h->run.times.linearize_ms = elapsed(h->str.ev[0], h->str.ev[1]);
+      if (h->run.rsTimed) h->run.times.rs_update_ms = elapsed(h->str.ev[8], h->str.ev[9]), h->run.rsTimed = false;
     }
-    h->times.schur_ms = elapsed(h->ev[2], h->ev[3]);
-    h->times.factor_ms = elapsed(h->ev[3], h->ev[4]);
-    h->times.solve_ms = elapsed(h->ev[4], h->ev[5]);
-    h->times.step_ms = elapsed(h->ev[10], h->ev[11]);
-    h->times.cost_ms = elapsed(h->ev[6], h->ev[7]);
-    h->linearized = false, h->factored = true;
+    h->run.times.schur_ms = elapsed(h->str.ev[2], h->str.ev[3]);
+    h->run.times.factor_ms = elapsed(h->str.ev[3], h->str.ev[4]);
+    h->run.times.solve_ms = elapsed(h->str.ev[4], h->str.ev[5]);
+    h->run.times.step_ms = elapsed(h->str.ev[10], h->str.ev[11]);
+    h->run.times.cost_ms = elapsed(h->str.ev[6], h->str.ev[7]);
+    h->run.linearized = false, h->run.factored = true;
     return 0;
   }
   int gradient_dot_step(int dontRetry, double* backRed) { return vb_gradient_dot_step(h, dontRetry, backRed); }
@@ -235,13 +231,13 @@ struct OptimizeOps {
     return 0;
   }
   int iteration_done(int it, double prevCost, double newCost, double damping, int) {
-    h->times.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->run.times.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (log && verbose) {
       char buf[512];
       snprintf(buf, sizeof(buf),
                "it %d cost %.12g -> %.12g lambda %.3g (t %.2f ms: lin %.2f schur %.2f factor %.2f solve %.2f)", it,
-               prevCost, newCost, damping, h->times.total_ms, h->times.linearize_ms, h->times.schur_ms,
-               h->times.factor_ms, h->times.solve_ms);
+               prevCost, newCost, damping, h->run.times.total_ms, h->run.times.linearize_ms, h->run.times.schur_ms,
+               h->run.times.factor_ms, h->run.times.solve_ms);
       log(buf, user);
     }
     return 0;
@@ -251,22 +247,22 @@ struct OptimizeOps {
 // Optimizer::optimize (Optimizer.cpp:768-1106).  An error after an iteration's backup restores the variables
 // of that iteration's linearization point before returning.
 int vb_optimize(vb_handle h, const vb_settings* sp, vb_log_cb log, vb_prestep_cb pre, void* user, vb_summary* out) {
-  if (!h || !h->finalized) return fail(VB_E_STATE, "vb_optimize before vb_finalize");
+  if (!h || !h->fin) return fail(VB_E_STATE, "vb_optimize before vb_finalize");
   vb_settings s;
   if (sp) s = *sp;
   else vb_default_settings(&s);
-  const bool preint = h->recomputePreint && h->pi.n > 0;
+  const bool preint = h->prob.recomputePreint && h->fin->pi.n > 0;
   // (no memory for the spare buffers: the plain controller, which needs none)
-  const bool speculate = !pre && !preint && !h->sharded && !h->partSet && specPrepare(h);
+  const bool speculate = !pre && !preint && !h->prob.sharded && !h->prob.partSet && specPrepare(h);
   OptimizeOps ops{h, s.max_num_iterations, s.verbose != 0, log, pre, user, preint, speculate};
   if (const int rc = viba_lm::lmRun(s, ops, out)) {
-    if (ops.backedUp && vb_restore(h) == 0) (void)hipStreamSynchronize(h->st);
-    (void)hipStreamSynchronize(h->st);
+    if (ops.backedUp && vb_restore(h) == 0) (void)hipStreamSynchronize(h->str.st);
+    (void)hipStreamSynchronize(h->str.st);
     return rc;
   }
   // (a speculative linearization left queued by a convergence stop is never committed; its buffers are
   // the spare ones)
-  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipStreamSynchronize(h->str.st));
   return 0;
 }
 

@@ -50,27 +50,25 @@ static_assert(VB_REPORT_MAX_GROUPS == kRepMaxGroups && VB_REPORT_MAX_EDGES == kR
 
 int reportCommon(vb_handle h, const char* what) {
   if (!h) return fail(VB_E_ARG, std::string(what) + ": null handle");
-  if (!h->finalized) return fail(VB_E_STATE, std::string(what) + " before vb_finalize");
+  if (!h->fin) return fail(VB_E_STATE, std::string(what) + " before vb_finalize");
   if (!wholeProblem(h))
     return fail(VB_E_UNSUPPORTED, std::string(what) + " needs the whole problem on this handle (no shard / partition)");
   HIPCHK(hipSetDevice(h->cfg.device));
-  ReportState& r = h->rep;
-  if (!r.posOfRow) {
-    std::vector<int32_t> pos(h->visRowOfPos.size());
-    for (size_t i = 0; i < pos.size(); i++) pos[h->visRowOfPos[i]] = (int32_t)i;
-    if (r.mem.put(&r.posOfRow, pos) || r.mem.zeroed(&r.err, 2) || r.mem.event(&r.ev[0]) || r.mem.event(&r.ev[1])) {
-      r.mem.release();  // a later call starts over instead of finding half a state
-      r.posOfRow = r.err = nullptr, r.ev[0] = r.ev[1] = nullptr;
-      return fail(VB_E_HIP, std::string(what) + ": could not allocate the report's device state");
-    }
+  if (!h->rep) {
+    std::vector<int32_t> pos(h->fin->visRowOfPos.size());
+    for (size_t i = 0; i < pos.size(); i++) pos[h->fin->visRowOfPos[i]] = (int32_t)i;
+    auto r = std::make_unique<ReportState>();
+    if (r->mem.put(&r->posOfRow, pos) || r->mem.zeroed(&r->err, 2) || r->mem.event(&r->ev[0]) || r->mem.event(&r->ev[1]))
+      return fail(VB_E_HIP, std::string(what) + ": could not allocate the report's device state");  // (r goes)
+    h->rep = std::move(r);
   }
   return 0;
 }
 
 int checkReportErr(vb_handle h) {
   int32_t e = 0;
-  HIPCHK(hipMemcpyAsync(&e, h->rep.err, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipMemcpyAsync(&e, h->rep->err, sizeof(int32_t), hipMemcpyDeviceToHost, h->str.st));
+  HIPCHK(hipStreamSynchronize(h->str.st));
   if (e & 1) return fail(VB_E_RANGE, "RollingShutterData::getEstimate: out of range (residual report)");
   return 0;
 }
@@ -86,7 +84,7 @@ int vb_factor_errors(vb_handle h, int kind, int64_t first, int64_t n, double* ra
                      double* sq_weighted, double* cost, uint8_t* valid) {
   if (int rc = reportCommon(h, "vb_factor_errors")) return rc;
   if (kind < 0 || kind >= 14) return fail(VB_E_ARG, "vb_factor_errors: bad factor kind");
-  const int64_t N = (int64_t)h->fint[kind].size();
+  const int64_t N = (int64_t)h->prob.fint[kind].size();
   if (first < 0 || n < 0 || first > N || n > N - first) return fail(VB_E_ARG, "vb_factor_errors: rows out of range");
   if (n == 0) return 0;
   const int m = kErrSize[kind];
@@ -97,14 +95,14 @@ int vb_factor_errors(vb_handle h, int kind, int64_t first, int64_t n, double* ra
       (sq_weighted && S.get(&R.sqw, n)) || (cost && S.get(&R.cost, n)) ||
       (valid && kind == VB_F_VISUAL && S.get(&R.valid, n)))
     return devFail(S, "vb_factor_errors: device allocation");
-  HIPCHK(hipMemsetAsync(h->rep.err, 0, sizeof(int32_t), h->st));
-  if (kind == VB_F_VISUAL) launch_visual_rows(h->d, h->rep.posOfRow, R, h->rep.err, h->st);
-  else launch_small_rows(h->d, kind, R, h->st);
+  HIPCHK(hipMemsetAsync(h->rep->err, 0, sizeof(int32_t), h->str.st));
+  if (kind == VB_F_VISUAL) launch_visual_rows(h->fin->d, h->rep->posOfRow, R, h->rep->err, h->str.st);
+  else launch_small_rows(h->fin->d, kind, R, h->str.st);
   HIPCHK(hipGetLastError());
-  if (download(raw, R.raw, (size_t)n * m, h->st) || download(sq_unweighted, R.squ, n, h->st) ||
-      download(sq_weighted, R.sqw, n, h->st) || download(cost, R.cost, n, h->st))
+  if (download(raw, R.raw, (size_t)n * m, h->str.st) || download(sq_unweighted, R.squ, n, h->str.st) ||
+      download(sq_weighted, R.sqw, n, h->str.st) || download(cost, R.cost, n, h->str.st))
     return VB_E_HIP;
-  if (valid && kind == VB_F_VISUAL && download(valid, R.valid, n, h->st)) return VB_E_HIP;
+  if (valid && kind == VB_F_VISUAL && download(valid, R.valid, n, h->str.st)) return VB_E_HIP;
   if (valid && kind != VB_F_VISUAL) std::fill(valid, valid + n, (uint8_t)1);  // only visual factors can fail
   return checkReportErr(h);
 }
@@ -122,15 +120,15 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
   for (int32_t e = 0; e < n_edges; e++)
     if (!std::isfinite(edges[e]) || (e > 0 && !(edges[e] > edges[e - 1])))
       return fail(VB_E_ARG, "vb_error_histogram: edges must be finite and strictly increasing");
-  const Dev& d = h->d;
-  const int64_t N = (int64_t)h->fint[kind].size();
+  const Dev& d = h->fin->d;
+  const int64_t N = (int64_t)h->prob.fint[kind].size();
   const bool visual = kind == VB_F_VISUAL;
   // the group of every item in the kernel's item order: obCostOrder positions (visual), rows (the rest)
   std::vector<uint8_t> grp;
   if (group_of_factor) {
     grp.resize(N);
     for (int64_t i = 0; i < N; i++) {
-      const int32_t g = group_of_factor[visual ? h->visRowOfPos[i] : i];
+      const int32_t g = group_of_factor[visual ? h->fin->visRowOfPos[i] : i];
       if (g < 0 || g >= n_groups) return fail(VB_E_ARG, "vb_error_histogram: group id outside [0, n_groups)");
       grp[i] = (uint8_t)g;
     }
@@ -145,18 +143,18 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
       S.get(&H.nFailing, n_groups) || (group_of_factor && S.get(&grpD, N)))
     return devFail(S, "vb_error_histogram: device allocation");
   H.edges = edgesD, H.grp = grpD;
-  hipStream_t st = h->st;
+  hipStream_t st = h->str.st;
   HIPCHK(hipMemcpyAsync(edgesD, edges, n_edges * sizeof(double), hipMemcpyHostToDevice, st));
   if (grpD && N) HIPCHK(hipMemcpyAsync(grpD, grp.data(), N, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(H.counts, 0, nb * sizeof(unsigned long long), st));
   HIPCHK(hipMemsetAsync(H.cost, 0, n_groups * sizeof(double), st));
   HIPCHK(hipMemsetAsync(H.nFactors, 0, n_groups * sizeof(unsigned long long), st));
   HIPCHK(hipMemsetAsync(H.nFailing, 0, n_groups * sizeof(unsigned long long), st));
-  HIPCHK(hipMemsetAsync(h->rep.err, 0, sizeof(int32_t), st));
-  HIPCHK(hipEventRecord(h->rep.ev[0], st));
+  HIPCHK(hipMemsetAsync(h->rep->err, 0, sizeof(int32_t), st));
+  HIPCHK(hipEventRecord(h->rep->ev[0], st));
   if (visual) {
     // a few workgroups per CU walk the positions: the table's flush is paid once per workgroup
-    launch_visual_hist(d, H, h->rep.err, h->numCUs * 8, st);
+    launch_visual_hist(d, H, h->rep->err, h->tune.numCUs * 8, st);
   } else if (N > 0) {
     const int m = kErrSize[kind];
     RepRows R;
@@ -168,15 +166,15 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
                        R.raw, R.squ, R.sqw, R.cost, H);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->rep.ev[1], st));
+  HIPCHK(hipEventRecord(h->rep->ev[1], st));
   std::vector<unsigned long long> cnt(nb), nf(n_groups), nx(n_groups);
   if (download(cnt.data(), H.counts, nb, st) || download(nf.data(), H.nFactors, n_groups, st) ||
       download(nx.data(), H.nFailing, n_groups, st) || download(cost, H.cost, n_groups, st))
     return VB_E_HIP;
   if (int rc = checkReportErr(h)) return rc;
   float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->rep.ev[0], h->rep.ev[1]));
-  h->rep.histMs = ms;
+  HIPCHK(hipEventElapsedTime(&ms, h->rep->ev[0], h->rep->ev[1]));
+  h->rep->histMs = ms;
   if (counts) std::copy(cnt.begin(), cnt.end(), counts);
   if (n_factors) std::copy(nf.begin(), nf.end(), n_factors);
   if (n_failing) std::copy(nx.begin(), nx.end(), n_failing);
@@ -185,7 +183,7 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
 
 int vb_report_device_ms(vb_handle h, double* ms) {
   if (!h || !ms) return fail(VB_E_ARG, "vb_report_device_ms: null argument");
-  *ms = h->rep.histMs;
+  *ms = h->rep ? h->rep->histMs : 0.0;
   return 0;
 }
 

@@ -133,47 +133,47 @@ extern "C" int vb_triangulate_points(int64_t n_tracks, const int64_t* start, con
 // off-diagonal tiles), averaged over `iters` launches, kernel-exact (hipExtLaunchKernelGGL events).
 // which: 0 potrf, 1 trsm (one tile), 2/3 update (one pair)
 extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us) {
-  if (!h || !h->finalized || iters <= 0) return fail(VB_E_STATE, "vb_bench_kernel needs a finalized handle");
+  if (!h || !h->fin || iters <= 0) return fail(VB_E_STATE, "vb_bench_kernel needs a finalized handle");
   DevOwner m;  // the scratch tiles and events of the call, freed on every path
   if (which >= 10) {  // kernels of the linearize / Schur phases alone, on the handle's own data
-    Dev& d = h->d;
+    Dev& d = h->fin->d;
     hipEvent_t e0, e1, evP;
     if (m.event(&e0) || m.event(&e1) || m.event(&evP, hipEventDisableTiming)) return devFail(m, "vb_bench_kernel: events");
-    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipStreamSynchronize(h->str.st));
     double total = 0;
     for (int it = 0; it < iters + 1; it++) {
-      HIPCHK(hipEventRecord(e0, h->st));
+      HIPCHK(hipEventRecord(e0, h->str.st));
       switch (which) {
         case 10:  // visual linearization (records)
-          launch_visual_lin(d, 0, 0, d.obB, d.obE, h->st);
-          launch_visual_lin(d, 0, 0, d.fB, d.fE, h->st);
+          launch_visual_lin(d, 0, 0, d.obB, d.obE, h->str.st);
+          launch_visual_lin(d, 0, 0, d.fB, d.fE, h->str.st);
           break;
-        case 12: launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->st); break;  // landmark elimination
-        case 13: launch_groups(d, 1e-5, h->st); break;                     // observation-group Gram blocks
-        case 14: launch_schur_products(d, 1e-5, h->st); break;             // Schur tile products
-        case 15: launch_visual_cost(d, 1, d.obB, d.obE, h->st); break;     // cost pass (visual)
+        case 12: launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->str.st); break;  // landmark elimination
+        case 13: launch_groups(d, 1e-5, h->str.st); break;                     // observation-group Gram blocks
+        case 14: launch_schur_products(d, 1e-5, h->str.st); break;             // Schur tile products
+        case 15: launch_visual_cost(d, 1, d.obB, d.obE, h->str.st); break;     // cost pass (visual)
         // the small factors (staging for 17 / 18 from an earlier 16) and the clear; they change the tiles
-        case 16: launch_small_eval(d, 0, d.gRed, h->st); break;
-        case 17: launch_small_assemble(d, 0, d.gRed, h->st, 1); break;
-        case 18: launch_small_assemble(d, 0, d.gRed, h->st, 2); break;
+        case 16: launch_small_eval(d, 0, d.gRed, h->str.st); break;
+        case 17: launch_small_assemble(d, 0, d.gRed, h->str.st, 1); break;
+        case 18: launch_small_assemble(d, 0, d.gRed, h->str.st, 2); break;
         case 19:
-          if (int rc = clearReduced(h, d, h->st)) return rc;
+          if (int rc = clearReduced(h, d, h->str.st)) return rc;
           break;
         // overlap probes (timing only: the products read the previous elimination's Y): landmark elimination
         // and tile products side by side (20) or in sequence (21); 22: elimination + groups side by side
         case 20:
         case 22:
-          HIPCHK(hipEventRecord(h->evFork, h->st));
-          HIPCHK(hipStreamWaitEvent(h->st2, h->evFork, 0));
-          if (which == 20) launch_schur_products(d, 1e-5, h->st2);
-          else launch_groups(d, 1e-5, h->st2);
-          HIPCHK(hipEventRecord(h->evJoin, h->st2));
-          launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->st);
-          HIPCHK(hipStreamWaitEvent(h->st, h->evJoin, 0));
+          HIPCHK(hipEventRecord(h->str.evFork, h->str.st));
+          HIPCHK(hipStreamWaitEvent(h->str.st2, h->str.evFork, 0));
+          if (which == 20) launch_schur_products(d, 1e-5, h->str.st2);
+          else launch_groups(d, 1e-5, h->str.st2);
+          HIPCHK(hipEventRecord(h->str.evJoin, h->str.st2));
+          launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->str.st);
+          HIPCHK(hipStreamWaitEvent(h->str.st, h->str.evJoin, 0));
           break;
         case 21:
-          launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->st);
-          launch_schur_products(d, 1e-5, h->st);
+          launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->str.st);
+          launch_schur_products(d, 1e-5, h->str.st);
           break;
         // the factorization (its streams) alone (23), and beside the tile products on stF (24); timing only
         // (the tiles are refactored in place, so their values are garbage after the first launch)
@@ -182,19 +182,19 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
           break;
         case 24:
         case 25: {  // 25: the products on stZ instead
-          hipStream_t ps = which == 24 ? h->stF : h->stZ;
-          HIPCHK(hipEventRecord(h->evFork, h->st));
-          HIPCHK(hipStreamWaitEvent(ps, h->evFork, 0));
+          hipStream_t ps = which == 24 ? h->str.stF : h->str.stZ;
+          HIPCHK(hipEventRecord(h->str.evFork, h->str.st));
+          HIPCHK(hipStreamWaitEvent(ps, h->str.evFork, 0));
           launch_schur_products(d, 1e-5, ps);
           HIPCHK(hipEventRecord(evP, ps));
           if (int rc = factorReduced(h, 0)) return rc;
-          HIPCHK(hipStreamWaitEvent(h->st, evP, 0));
+          HIPCHK(hipStreamWaitEvent(h->str.st, evP, 0));
           break;
         }
         default: return fail(VB_E_ARG, "vb_bench_kernel: unknown kernel");
       }
-      HIPCHK(hipEventRecord(e1, h->st));
-      HIPCHK(hipStreamSynchronize(h->st));
+      HIPCHK(hipEventRecord(e1, h->str.st));
+      HIPCHK(hipStreamSynchronize(h->str.st));
       float ms = 0;
       HIPCHK(hipEventElapsedTime(&ms, e0, e1));
       if (it > 0) total += ms;
@@ -203,12 +203,12 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
     // the timed launches left partial sums in the striped reduction slots (no fold_red after them) and
     // overwrote tiles, gradient and staging: clear the slots, and make the handle re-linearize before
     // any solve or cost comparison uses that state
-    HIPCHK(hipMemsetAsync(d.redS, 0, 64 * 8 * sizeof(double), h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    h->linearized = h->factored = false;
+    HIPCHK(hipMemsetAsync(d.redS, 0, 64 * 8 * sizeof(double), h->str.st));
+    HIPCHK(hipStreamSynchronize(h->str.st));
+    h->run.linearized = h->run.factored = false;
     return checkErr(h) == VB_E_HIP ? VB_E_HIP : 0;
   }
-  Dev d = h->d;  // copy: tiles / err redirected to scratch
+  Dev d = h->fin->d;  // copy: tiles / err redirected to scratch
   std::vector<double> A(TS * TS), B(TS * TS);
   uint64_t sd = 12345;
   auto rnd = [&] { sd = sd * 6364136223846793005ULL + 1442695040888963407ULL; return ((sd >> 11) * 0x1.0p-53) - 0.5; };
@@ -235,16 +235,16 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
   const size_t tb = TS * TS * sizeof(double);
   for (int it = 0; it < iters + 1; it++) {
     // tile 0: SPD (factored first for trsm/update), tile 1: off-diagonal, tile 2: SPD target
-    HIPCHK(hipMemcpyAsync(tiles, A.data(), tb, hipMemcpyHostToDevice, h->st));
-    HIPCHK(hipMemcpyAsync(tiles + TS * TS, B.data(), tb, hipMemcpyHostToDevice, h->st));
-    HIPCHK(hipMemcpyAsync(tiles + 2 * TS * TS, A.data(), tb, hipMemcpyHostToDevice, h->st));
-    if (which != 0) launch_potrf(d, colT, targ, 1, dinv, h->st);
+    HIPCHK(hipMemcpyAsync(tiles, A.data(), tb, hipMemcpyHostToDevice, h->str.st));
+    HIPCHK(hipMemcpyAsync(tiles + TS * TS, B.data(), tb, hipMemcpyHostToDevice, h->str.st));
+    HIPCHK(hipMemcpyAsync(tiles + 2 * TS * TS, A.data(), tb, hipMemcpyHostToDevice, h->str.st));
+    if (which != 0) launch_potrf(d, colT, targ, 1, dinv, h->str.st);
     g_prof.start = e0, g_prof.stop = e1, g_prof.consumed = false;
-    if (which == 0) launch_potrf(d, colT, targ, 1, dinv, h->st);
-    else if (which == 1) launch_trsm(d, colT, colT + 2, targ, 1, dinv, h->st);
-    else launch_fanin(d, pairs, fpD, 1, h->st);
+    if (which == 0) launch_potrf(d, colT, targ, 1, dinv, h->str.st);
+    else if (which == 1) launch_trsm(d, colT, colT + 2, targ, 1, dinv, h->str.st);
+    else launch_fanin(d, pairs, fpD, 1, h->str.st);
     g_prof = ProfSlot();
-    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipStreamSynchronize(h->str.st));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     if (it > 0) total += ms;  // first launch: warm-up
