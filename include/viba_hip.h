@@ -32,6 +32,9 @@
  *   Optimizer::applyStep (Optimizer.cpp:121-134)               vb_apply_step
  *   backupVariables / restoreVariables (Optimizer.cpp:99-119)  vb_backup / vb_restore
  *   Optimizer::optimize (Optimizer.cpp:768-1106)               vb_optimize
+ *   Settings::triggerDebuggingOfNonlinearities: Factor::       vb_set_inspect_iteration,
+ *     singleExpectedDelta + compareExpectedValues                vb_inspect_nonlinearities,
+ *     (Factor.h:470-540, Optimizer.cpp:727-766, 861-883)         vb_factor_expected_delta
  *   SingleSessionAdapter::compareCalibrationVsFactory, the     vb_calib_projection_offsets
  *     projection offsets (viba/single_session/
  *     EvalCalibration.cpp:57-116)
@@ -620,6 +623,60 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
                        int64_t* n_failing);
 /* device time [ms] of the last vb_error_histogram's kernels (measurement aid) */
 int vb_report_device_ms(vb_handle h, double* ms);
+
+/* ---------------------------------------------------------------- non-linearity inspection
+ * ark_vi_ba's --trigger-debugging-of-nonlinearities N (Optimizer::Settings::triggerDebuggingOfNonlinearities,
+ * lib/small_thing/Optimizer.h:84; read at Optimizer.cpp:861-883 and interfaces/ark/main_AriaKit_ViBa.cpp:103-106):
+ * in iteration N the reference does not take the step; it asks every factor for singleExpectedDelta(i, step)
+ * (Factor.h:470-540), applies the step, evaluates singleCost(i) again (compareExpectedValues,
+ * Optimizer.cpp:727-766) and prints the factors whose linear prediction is furthest off.
+ * Per factor, with e the functor's return, P its precision matrix (the inertial kinds' inverse rvpCov, the
+ * pose prior's H, otherwise the identity) and (rho, rho') = loss.jet2(e'Pe):
+ *   w = rho' P e;  per variable slot that is neither constant, unregistered (-1) nor gravity: g_s = J_s^T w
+ *   v0 = 0.5 rho,  delta = sum_s step_s . g_s,  grad_norm = sqrt(sum_s |g_s|^2)
+ * A failing factor (visual kind only) gets v0 = -1, delta = 0, grad_norm = 0 (the reference's {-1, 0, 0}); a
+ * visual factor beyond the loss cutoff has rho' = 0, so delta = grad_norm = 0 with v0 = 0.5 (2ak - a^2).
+ * The Jacobians are evaluated in fp64 in both builds (the stored fp32 records of the mixed build are not read). */
+
+/* Factor.h:470-540 for rows [first, first + n) of `kind` (vb_add_factors order), at the current
+ * variables, with the step the handle holds (which = 0 step, 1 sub-step). Any output may be NULL.
+ * Needs vb_finalize and a step on the device: vb_damp_factor_solve (or an iteration of vb_optimize) has run,
+ * for which = 1 also vb_solve_with_new_gradient; otherwise VB_E_STATE.  VB_E_UNSUPPORTED on a landmark shard
+ * or a partitioned rank, VB_E_RANGE for an out-of-range rolling-shutter lookup, VB_E_ARG for a bad kind,
+ * rows outside the kind's factors or a bad `which`.  Reads the variables, the rolling-shutter tables as they
+ * are and the step; writes only buffers of its own: the cost cache, the scalar / error-word slots, the step,
+ * the small factors' staging of the last linearization and the speculative buffers stay as they are. */
+int vb_factor_expected_delta(vb_handle h, int kind, int64_t first, int64_t n, int which,
+                             double* v0, double* delta, double* grad_norm);
+
+/* Optimizer.cpp:861-872 + compareExpectedValues (:727-766): expected values at the current variables,
+ * backupVariables, applyStep(which), singleCost of every factor, score, the k worst.
+ *   score = fabs((v0 + delta) - v1) / (fmin(grad_norm, 1000.0) + 1.0)   (these operations, in this order)
+ * A factor takes part when it is valid at both points and bit `kind` of kind_mask is set (the reference: all
+ * 14 bits); n_compared counts those.  The n_found = min(k, n_compared) results are ordered by descending
+ * score, ties by lower kind, then lower row; a NaN score counts (and is returned) as +inf.  v1 is the `cost`
+ * of vb_factor_errors at the stepped variables, bit for bit.  Outputs (each may be NULL) hold k entries.
+ * The selection is exact and reproducible (integer keys, no floating-point atomics).
+ * On return the variables hold the step and the backup holds the linearization point, exactly as vb_backup +
+ * vb_apply_step(which) leave them (the reference returns from optimize the same way); vb_restore goes back.
+ * VB_E_RANGE found at the linearization point leaves the variables there.  problematicFactorDebugFunc
+ * (Optimizer.cpp:874-880) is a GUI hook and has no counterpart.
+ * Errors as vb_factor_expected_delta; VB_E_ARG also for k outside [1, VB_INSPECT_MAX_K], an empty mask or
+ * bits above kind 13. */
+#define VB_INSPECT_MAX_K 64
+int vb_inspect_nonlinearities(vb_handle h, int which, uint32_t kind_mask, int32_t k,
+                              int32_t* kinds, int64_t* rows, double* score, double* v0, double* delta,
+                              double* v1, double* grad_norm, int32_t* n_found, int64_t* n_compared);
+
+/* Optimizer::Settings::triggerDebuggingOfNonlinearities for vb_optimize: iteration N (1-based as in the
+ * reference: iterationNum + 1 == N; 0 or negative = off) of the next vb_optimize calls stops after
+ * damp + factor + solve, runs vb_inspect_nonlinearities(which 0, all kinds, k) and ends the run with
+ * return 0 and a zeroed vb_summary (the reference's `return {}`); vb_inspection_result fetches it
+ * (the last inspection's result, by either path; n_found 0 when there is none). */
+int vb_set_inspect_iteration(vb_handle h, int iteration, int32_t k);
+int vb_inspection_result(vb_handle h, int32_t* kinds, int64_t* rows, double* score, double* v0, double* delta,
+                         double* v1, double* grad_norm, int32_t* n_found, int64_t* n_compared);
+int vb_inspect_device_ms(vb_handle h, double ms[3]); /* x0 pass, x1 pass, selection of the last call */
 
 /* ---------------------------------------------------------------- calibration against factory
  * The image projection offsets of SingleSessionAdapter::compareCalibrationVsFactory

@@ -653,7 +653,7 @@ def save_outputs(out_dir: str, engine, p: SessionProblem, sd: SessionData):
 def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, settings: InitSettings | None = None,
                 optimizer_settings=None, refine: bool = True, log=print, show_histogram: bool = False,
                 simple_stats: bool = False, triangulate=None, eval_calib_vs_factory: bool | None = None,
-                optimize: bool = True):
+                optimize: bool = True, trigger_debugging_of_nonlinearities: int = -1, inspect_k: int = 5):
     """ark_vi_ba (interfaces/ark/main_AriaKit_ViBa.cpp:32-133) on a session folder: load, build indices,
     build the problem, rolling-shutter tables, refinePoints, Optimizer::optimize (with the per-iteration
     rolling-shutter rebuild and, under settings.recompute_preint, the preintegration recompute of the
@@ -665,7 +665,11 @@ def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, se
     final histogram and before the outputs, log the estimated calibration against the factory one
     (calib_eval.compare_calibration_vs_factory, main_AriaKit_ViBa.cpp:116-120); it also runs with
     optimize=False (--dont-optimize, :74), which skips Optimizer::optimize and its histogram and returns None
-    as the summary.  Returns (engine, problem, summary)."""
+    as the summary.  trigger_debugging_of_nonlinearities (--trigger-debugging-of-nonlinearities N,
+    Optimizer.cpp:861-883): when positive, iteration N of optimize inspects its step in place of taking it
+    (engine.set_inspect_iteration); the inspect_k worst factors are logged as the reference prints them, then
+    `Exiting... happy debugging!` (main_AriaKit_ViBa.cpp:103-106), and the run returns (engine, problem, None):
+    no second histogram, no calibration comparison, no output files.  Returns (engine, problem, summary)."""
     from .engine import HipEngine, Settings
     s = settings or InitSettings()
     sd = SessionData.load(in_dir, load_imu=True)
@@ -690,6 +694,14 @@ def run_session(in_dir: str, out_dir: str | None = None, engine_factory=None, se
     histogram()
     summary = None
     if optimize:
+        if trigger_debugging_of_nonlinearities > 0:
+            from .nonlinearity import format_nonlinearities
+            e.set_inspect_iteration(trigger_debugging_of_nonlinearities, inspect_k)
+            e.optimize(optimizer_settings or Settings.default())
+            if log:
+                log(format_nonlinearities(e.inspection_result()))
+                log("Exiting... happy debugging!")
+            return e, p, None
         summary = e.optimize(optimizer_settings or Settings.default())
         if log:
             log(f"[ark] optimize: {summary.initial_cost:.6g} -> {summary.final_cost:.6g} in {summary.num_iterations} iterations")

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("VIBA_LIB_DIR", os.path.join(HERE, "lib"))
 HIP_SOURCES = ["factors.hip", "schur.hip", "solver.hip", "rs.hip", "preint.hip", "pcg.hip", "selinv.hip", "lowprec.hip", "api.hip", "factor_host.hip", "pcg_host.hip",
                "optimize.hip", "symbolic.hip", "finalize.hip", "covariances.hip", "pointcov.hip", "report.hip", "multi.hip", "tools.hip",
-               "triangulate.hip", "calib_eval.hip"]
+               "triangulate.hip", "calib_eval.hip", "inspect.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("VIBA_OFFLOAD_ARCH", "gfx950")
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",

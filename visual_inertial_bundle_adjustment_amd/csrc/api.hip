@@ -618,7 +618,7 @@ int vb_damp_factor_solve(vb_handle h, double lambda, double* model_cost_reductio
   h->run.times.factor_ms = elapsed(h->str.ev[3], h->str.ev[4]);
   h->run.times.solve_ms = elapsed(h->str.ev[4], h->str.ev[5]);
   if (model_cost_reduction) *model_cost_reduction = 0.5 * dotv;
-  h->run.linearized = false, h->run.factored = true;
+  h->run.linearized = false, h->run.factored = true, h->run.haveStep = true;
   return 0;
 }
 
@@ -656,7 +656,9 @@ int vb_solve_with_new_gradient(vb_handle h) {
   }
   backSubstitute(h, 1);
   HIPCHK(hipStreamSynchronize(h->str.st));
-  return checkErr(h);
+  if (int rc = checkErr(h)) return rc;
+  h->run.haveSub = true;
+  return 0;
 }
 
 int vb_set_solver(vb_handle h, int solver_type, int pcg_max_iterations, double pcg_desired_residual) {

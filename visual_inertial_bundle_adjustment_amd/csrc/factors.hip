@@ -12,6 +12,7 @@
 //                         factor, scattered into the reduced tiles / gradient with fp64 atomics.
 #include "device_math.hpp"
 #include "engine.hpp"
+#include "inspect.hpp"
 #include "report.hpp"
 #include <algorithm>
 
@@ -434,6 +435,111 @@ __global__ void __launch_bounds__(256) visual_report_kernel(Dev d, const int32_t
     }
   }
   if (Hist) rep_flush(tab, H);
+}
+
+// singleExpectedDelta of the visual factors (Factor.h:470-540; inspect.hpp): the linearization's evaluation
+// (vis_eval<true> / rs_eval<true>, fp64 in both builds; the stored records d.Jt are not read) at the current
+// variables and tables, one lane per item.  With w = rho' e the lane forms J_s^T w block by block and dots it
+// with the step of the slot: stepPt + 3 ptLm[point], stepRed + rvOff[obRed[4 o + slot]]; a slot with reduced
+// id -1 (constant, unregistered, no velocity) is skipped.  A failing factor gets (-1, 0, 0); beyond the loss
+// cutoff rho' = 0, so delta = gnorm = 0 with v0 = 0.5 (2 a k - a^2).
+// The point, pose, extrinsics and velocity blocks stay in registers; the 2 x 17 intrinsics block is the
+// lane's 35-double row of LDS (odd stride: a plane's 64 lanes hit distinct banks), as visual_lin_kernel keeps
+// it out of registers: 252 VGPRs, no scratch, 2 waves per SIMD (35 KB per 2-wave block, 4 blocks per CU).
+// All in registers it took 256 VGPRs + 52 AGPRs at 1 wave per SIMD (62 VGPRs spilled when held to 2) and ran
+// the whole x0 pass 17 % slower at config C.
+//   posOfRow == nullptr: item t = position R.first + t of obCostOrder (global shutter first: a wave takes
+//                        one evaluation path)
+//   otherwise:           item t = row R.first + t of vb_add_factors order, stored at t, coalesced
+// One kernel for both, so a row's numbers do not depend on the mode.  Reads neither the ResultCache nor the
+// reduction / error slots of the LM loop (err is the caller's own word).
+constexpr int kInsBlock = 128, kInsJ = 35;
+__global__ void __launch_bounds__(kInsBlock) visual_expected_kernel(Dev d, const int32_t* posOfRow, InsRows R,
+                                                                    int32_t* err) {
+  const int64_t t = (int64_t)blockIdx.x * kInsBlock + threadIdx.x;
+  if (t >= R.n) return;
+  const int64_t i = posOfRow ? posOfRow[R.first + t] : R.first + t;
+  const int4 pa = reinterpret_cast<const int4*>(d.obPack)[2 * i], pb = reinterpret_cast<const int4*>(d.obPack)[2 * i + 1];
+  // the slots' landmark / reduced ids and step offsets, loaded before the evaluation: behind it their two
+  // dependent loads cost nothing, after it every slot's branch waited for its own chain
+  const int32_t lm = d.ptLm[pa.y];
+  const int4 rd = reinterpret_cast<const int4*>(d.obRed)[pa.x];
+  const int64_t oPose = rd.x >= 0 ? d.rvOff[rd.x] : 0, oExtr = rd.y >= 0 ? d.rvOff[rd.y] : 0;
+  const int64_t oIntr = rd.z >= 0 ? d.rvOff[rd.z] : 0, oVel = rd.w >= 0 ? d.rvOff[rd.w] : 0;
+  const int dimIntr = rd.z >= 0 ? d.rvDim[rd.z] : 0;
+  __shared__ double jl[kInsBlock * kInsJ];
+  double* ji = jl + threadIdx.x * kInsJ;
+  VisOut v;
+  v.Jintr = ji;
+  bool oor = false, ok;
+  const double* obsC = d.obCP + i * 6;
+  const double* Xp = d.var[0] + (int64_t)pa.y * 3;
+  v3 X = mk(Xp[0], Xp[1], Xp[2]);
+  se3 Tbw = se3_load(d.var[1] + (int64_t)pa.z * 7);
+  se3 Tcb = se3_load(d.var[5] + (int64_t)pa.w * 7);
+  const double* cam = d.var[4] + (int64_t)pb.x * 24;
+  const int rs = pb.y;
+  if (rs < 0) {
+    ok = vis_eval<true>(obsC, X, Tbw, Tcb, cam, v);
+#pragma unroll
+    for (int q = 0; q < 6; q++) v.Jvel[q] = 0.0;
+  } else {
+    const double* vp = d.var[2] + (int64_t)pb.z * 3;
+    ok = rs_eval<true>(d, obsC, rs, X, Tbw, Tcb, cam, mk(vp[0], vp[1], vp[2]), (pb.w & 1) != 0, (pb.w & 2) != 0, v, &oor);
+    if (oor) atomicOr(err, 1);
+  }
+  double v0 = -1.0, delta = 0.0, g2 = 0.0;
+  if (ok) {
+    const double s = v.e[0] * v.e[0] + v.e[1] * v.e[1];
+    double rho, drho;
+    huber_jet2(d.reproj.a, d.reproj.b, d.reproj.k2, d.reproj.h, s, rho, drho);
+    v0 = 0.5 * rho;
+    const double w0 = drho * v.e[0], w1 = drho * v.e[1];
+    if (lm >= 0) {
+      const double* sp = R.stepPt + (int64_t)lm * 3;
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const double g = v.Jpt[j] * w0 + v.Jpt[3 + j] * w1;
+        delta += sp[j] * g, g2 += g * g;
+      }
+    }
+    if (rd.x >= 0) {
+      const double* sp = R.stepRed + oPose;
+#pragma unroll
+      for (int j = 0; j < 6; j++) {
+        const double g = v.Jpose[j] * w0 + v.Jpose[6 + j] * w1;
+        delta += sp[j] * g, g2 += g * g;
+      }
+    }
+    if (rd.y >= 0) {
+      const double* sp = R.stepRed + oExtr;
+#pragma unroll
+      for (int j = 0; j < 6; j++) {
+        const double g = v.Jextr[j] * w0 + v.Jextr[6 + j] * w1;
+        delta += sp[j] * g, g2 += g * g;
+      }
+    }
+    if (rd.z >= 0) {
+      // tangent: the projection parameters, then readout time / time offset where estimated (<= 17)
+      const double* sp = R.stepRed + oIntr;
+#pragma unroll
+      for (int j = 0; j < 17; j++) {
+        if (j < dimIntr) {
+          const double g = ji[j] * w0 + ji[17 + j] * w1;
+          delta += sp[j] * g, g2 += g * g;
+        }
+      }
+    }
+    if (rd.w >= 0) {
+      const double* sp = R.stepRed + oVel;
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const double g = v.Jvel[j] * w0 + v.Jvel[3 + j] * w1;
+        delta += sp[j] * g, g2 += g * g;
+      }
+    }
+  }
+  R.v0[t] = v0, R.delta[t] = delta, R.gnorm[t] = sqrt(g2);
 }
 
 // ------------------------------------------------------------------ small factors
@@ -1015,6 +1121,83 @@ __global__ void __launch_bounds__(64) small_report_kernel(Dev d, SmallArgs a, in
   small_case_report<13, LO, HI>(d, a, fk, k, R);
 }
 
+// singleExpectedDelta of the small kinds (Factor.h:470-540; inspect.hpp), two launches.
+// 1. small_eval<FK> with Jacobians (the linearization's instantiation, mode 1), one lane per factor of rows
+//    [first, a.n), over a copy of Dev whose staging pointers are the inspection's own (launch_small_expected):
+//    the Jacobian blocks, [rho', whitened residual] and meta go to slot k - first there, and v0 = 0.5 rho to
+//    v0[k - first].  d.sJ / d.sE / d.sMeta of the last linearization, the reduction and error slots are
+//    neither read nor written.
+template <int FK, int LO, int HI>
+__device__ __forceinline__ void small_case_expected(const Dev& d, const SmallArgs& a, int fk, int64_t k, int64_t first,
+                                                    double* v0) {
+  if constexpr (FK >= LO && FK <= HI) {
+    if (fk == FK) {
+      const double c = small_eval<FK>(d, a, k);
+      if (k < a.n) v0[k - first] = c;
+    }
+  }
+}
+template <int LO, int HI>
+__global__ void __launch_bounds__(64) small_expected_eval_kernel(Dev d, SmallArgs a, int fk, int64_t first, double* v0) {
+  const int64_t k = first + (int64_t)blockIdx.x * 64 + threadIdx.x;
+  small_case_expected<1, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<2, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<3, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<4, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<5, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<6, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<7, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<8, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<9, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<10, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<11, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<12, LO, HI>(d, a, fk, k, first, v0);
+  small_case_expected<13, LO, HI>(d, a, fk, k, first, v0);
+}
+// 2. one wave per staged factor (4 per workgroup): w = rho' P e = rho' U^T (U e) from the whitened residual
+//    (P = U^T U; no U: w = rho' e), lane r < m; then the lanes over the columns of every slot with a reduced
+//    id (constant, unregistered and gravity slots have none): g = J_col^T w from the raw Jacobian, its product
+//    with the step at rvOff[red] + j and its square, summed over the wave in a fixed order.  The calibration
+//    kinds' blocks hold their enabled entries only (dim columns), as the step does.
+__global__ void __launch_bounds__(256) small_expected_dot_kernel(Dev d, InsStage S, int fk, InsRows R) {
+  __shared__ double wl[4][kMaxM + 1];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t slot = (int64_t)blockIdx.x * 4 + wave;
+  if (slot >= R.n) return;
+  const int32_t* mt = S.sMeta + slot * kSmallMeta;
+  const int m = mt[0], nv = mt[2], uoff = mt[3];
+  const double* Jg = S.sJ + slot * kSmallJ;
+  const double* se = S.sE + slot * kSmallE;
+  const double drho = se[0];
+  if (lane < m) {
+    double x = se[1 + lane];
+    if (uoff >= 0) {
+      const double* U = d.sf[fk].consts + uoff;
+      x = 0.0;
+      for (int i = 0; i < m; i++) x += U[i * m + lane] * se[1 + i];
+    }
+    wl[wave][lane] = drho * x;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  double dl = 0.0, g2 = 0.0;
+  for (int s = 0; s < nv; s++) {
+    const int red = mt[5 + s];
+    if (red < 0) continue;
+    const int col = mt[15 + s], dim = mt[25 + s];
+    const double* sp = R.stepRed + d.rvOff[red];
+    for (int j = lane; j < dim; j += 64) {
+      double g = 0.0;
+      for (int r = 0; r < m; r++) g += Jg[r * kMaxCols + col + j] * wl[wave][r];
+      dl += sp[j] * g, g2 += g * g;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) dl += __shfl_xor(dl, off, 64), g2 += __shfl_xor(g2, off, 64);
+  if (lane == 0) R.delta[slot] = dl, R.gnorm[slot] = sqrt(g2);
+}
+
 // Assembly of the staged small factors, one wave per factor (4 per workgroup): whitened Jacobian
 // U J in LDS (lane = column), gradient rho' J^T e (mode 0 / 1) and, in mode 0, the Gauss-Newton
 // block rho' J^T J over the factor's non-constant columns, lane-parallel over the lower-triangle
@@ -1443,6 +1626,26 @@ void launch_small_rows(const Dev& d, int fk, const RepRows& R, hipStream_t st) {
   const dim3 grid((unsigned)((R.n + 63) / 64));
   if (fk <= 3) hipLaunchKernelGGL((small_report_kernel<1, 3>), grid, dim3(64), 0, st, d, a, fk, R);
   else hipLaunchKernelGGL((small_report_kernel<4, 13>), grid, dim3(64), 0, st, d, a, fk, R);
+}
+
+// non-linearity inspection (inspect.hpp)
+void launch_visual_expected(const Dev& d, const int32_t* posOfRow, const InsRows& R, int32_t* err, hipStream_t st) {
+  if (R.n <= 0) return;
+  hipLaunchKernelGGL(visual_expected_kernel, dim3((unsigned)((R.n + kInsBlock - 1) / kInsBlock)), dim3(kInsBlock), 0, st, d,
+                     posOfRow, R, err);
+}
+void launch_small_expected(const Dev& d, int fk, const InsRows& R, const InsStage& S, hipStream_t st) {
+  if (R.n <= 0 || R.n > S.cap) return;
+  // the evaluation's view of the handle: the inspection's staging, row R.first at slot 0
+  Dev di = d;
+  di.sJ = S.sJ, di.sE = S.sE, di.sMeta = S.sMeta;
+  di.sf[fk].stage = -R.first;
+  const SmallFactors& f = d.sf[fk];
+  const SmallArgs a{R.first + R.n, f.vars, f.consts, f.nc, 1, nullptr};
+  const dim3 grid((unsigned)((R.n + 63) / 64));
+  if (fk <= 3) hipLaunchKernelGGL((small_expected_eval_kernel<1, 3>), grid, dim3(64), 0, st, di, a, fk, R.first, R.v0);
+  else hipLaunchKernelGGL((small_expected_eval_kernel<4, 13>), grid, dim3(64), 0, st, di, a, fk, R.first, R.v0);
+  hipLaunchKernelGGL(small_expected_dot_kernel, dim3((unsigned)((R.n + 3) / 4)), dim3(256), 0, st, d, S, fk, R);
 }
 
 void launch_small_assemble(const Dev& d, int mode, double* gOut, hipStream_t st, int part = 3);

@@ -266,6 +266,10 @@ struct RunState {
   int32_t pcgIters = 0;
   double pcgRelRes = 0.0;
   int faultNegModelRedIt = -1, faultFailIt = -1;  // vb_debug_negate_model_reduction / _fail_iteration (tests)
+  // a step / sub-step is on the device (vb_damp_factor_solve / vb_solve_with_new_gradient have run):
+  // vb_factor_expected_delta and vb_inspect_nonlinearities need one
+  bool haveStep = false, haveSub = false;
+  int inspectIt = 0, inspectK = 5;  // vb_set_inspect_iteration (1-based iteration of vb_optimize, 0: off)
 };
 
 // everything vb_finalize makes (doFinalize, finalize.hip); the handle is finalized when it has one
@@ -360,6 +364,19 @@ struct ReportState {
   double histMs = 0.0;  // device time of the last vb_error_histogram's kernels
 };
 
+// the non-linearity inspection (inspect.hip): its device state, made at its first call, and the last result
+struct InspectState {
+  DevOwner mem;
+  int32_t *rowOfPos = nullptr, *posIdent = nullptr;  // position of obCostOrder -> visual row; the identity map
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // x0 [0, 1], x1 [2, 3], selection [3, 4]
+  double ms[3] = {0.0, 0.0, 0.0};  // x0 pass, x1 pass, selection of the last vb_inspect_nonlinearities
+  int32_t nFound = 0;
+  int64_t nCompared = 0;
+  int32_t kinds[VB_INSPECT_MAX_K];
+  int64_t rows[VB_INSPECT_MAX_K];
+  double score[VB_INSPECT_MAX_K], v0[VB_INSPECT_MAX_K], delta[VB_INSPECT_MAX_K], v1[VB_INSPECT_MAX_K], gnorm[VB_INSPECT_MAX_K];
+};
+
 // per-kernel-family device timing (vb_profile_kernel): event pairs around every launch
 struct ProfState {
   DevOwner mem;
@@ -384,6 +401,7 @@ struct vb_handle_s {
   std::unique_ptr<PcgState> pcg;
   std::unique_ptr<RefineState> refine;
   std::unique_ptr<ReportState> rep;
+  std::unique_ptr<InspectState> ins;
   ProfState prof;
 };
 

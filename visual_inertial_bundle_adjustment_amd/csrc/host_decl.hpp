@@ -43,6 +43,13 @@ void backSubstitute(vb_handle h, int which);
 bool pcgMode(vb_handle h);
 int precondInit(vb_handle h);
 int pcgSolve(vb_handle h);
+// the residual report's entry checks and device state, its error word (report.hip)
+int reportCommon(vb_handle h, const char* what);
+int checkReportErr(vb_handle h);
+// vb_inspect_nonlinearities into the handle's InspectState (inspect.hip); kInspectStop: the private return of
+// vb_optimize's iteration primitive that ends the run after the inspected iteration
+constexpr int kInspectStop = 1;
+int inspectRun(vb_handle h, int which, uint32_t kindMask, int32_t k);
 // vb_finalize (finalize.hip)
 int doFinalize(vb_handle h);
 // is the whole problem on this handle (no landmark shard, no partition)?  vb_refine_points alone accepts a

@@ -141,10 +141,14 @@ struct OptimizeOps {
       if (pre) pre(it, user);
       if ((rc = linearizeEnqueue(h, 1, dontRetry))) return rc;
     }
+    // (the iteration before it queued no speculative linearization: inspectNext below)
+    if (h->run.inspectIt > 0 && it + 1 == h->run.inspectIt) return inspectIteration(damping);
     // damp + eliminate + factor + solve, backup, box-plus and the cost pass queued back to back; the host
     // reads their scalars (costs, CostStats, model reduction, step ratios) and errors once, after the cost
     // pass: none of them changes what the queued work does
-    const bool specNext = speculate && it + 1 < maxIt;
+    // no speculative linearization in flight across an inspected iteration (vb_set_inspect_iteration)
+    const bool inspectNext = h->run.inspectIt > 0 && it + 2 == h->run.inspectIt;
+    const bool specNext = speculate && it + 1 < maxIt && !inspectNext;
     const bool early = specNext && smallHere(h, 0) && h->tune.specEarly;
     h->run.clearWanted = early && h->tune.clearInFactor, h->run.clearQueued = false;
     rc = dampFactorSolveEnqueue(h, damping, false);
@@ -213,8 +217,20 @@ struct OptimizeOps {
     h->run.times.solve_ms = elapsed(h->str.ev[4], h->str.ev[5]);
     h->run.times.step_ms = elapsed(h->str.ev[10], h->str.ev[11]);
     h->run.times.cost_ms = elapsed(h->str.ev[6], h->str.ev[7]);
-    h->run.linearized = false, h->run.factored = true;
+    h->run.linearized = false, h->run.factored = true, h->run.haveStep = true;
     return 0;
+  }
+  // Optimizer.cpp:861-883 (Settings::triggerDebuggingOfNonlinearities): after this iteration's linearization
+  // and solve, the inspection in place of backup / applyStep / cost; kInspectStop ends lmRun (vb_optimize
+  // turns it into success with a zeroed summary, the reference's `return {}`).  No speculative work is queued.
+  int inspectIteration(double damping) {
+    int rc;
+    if ((rc = dampFactorSolveEnqueue(h, damping, false))) return rc;
+    double r[17];
+    if ((rc = readRedErr(h, r, 17))) return rc;
+    h->run.linearized = false, h->run.factored = true, h->run.haveStep = true;
+    if ((rc = inspectRun(h, 0, (1u << 14) - 1, h->run.inspectK))) return rc;
+    return kInspectStop;
   }
   int gradient_dot_step(int dontRetry, double* backRed) { return vb_gradient_dot_step(h, dontRetry, backRed); }
   int scale_step(double f) { return vb_scale_step(h, f); }
@@ -255,7 +271,13 @@ int vb_optimize(vb_handle h, const vb_settings* sp, vb_log_cb log, vb_prestep_cb
   // (no memory for the spare buffers: the plain controller, which needs none)
   const bool speculate = !pre && !preint && !h->prob.sharded && !h->prob.partSet && specPrepare(h);
   OptimizeOps ops{h, s.max_num_iterations, s.verbose != 0, log, pre, user, preint, speculate};
+  if (h->run.inspectIt > 0 && h->ins) h->ins->nFound = 0, h->ins->nCompared = 0;
   if (const int rc = viba_lm::lmRun(s, ops, out)) {
+    if (rc == kInspectStop) {  // the inspected iteration ended the run: the reference's `return {}`
+      if (out) *out = vb_summary{};
+      HIPCHK(hipStreamSynchronize(h->str.st));
+      return 0;
+    }
     if (ops.backedUp && vb_restore(h) == 0) (void)hipStreamSynchronize(h->str.st);
     (void)hipStreamSynchronize(h->str.st);
     return rc;

@@ -48,6 +48,9 @@ namespace {
 constexpr int kErrSize[14] = {2, 9, 9, 9, 3, 23, 17, 6, 6, 6, 23, 17, 6, 6};
 static_assert(VB_REPORT_MAX_GROUPS == kRepMaxGroups && VB_REPORT_MAX_EDGES == kRepMaxEdges, "caps of the LDS bin table");
 
+}  // namespace
+
+// (shared with the non-linearity inspection, inspect.hip)
 int reportCommon(vb_handle h, const char* what) {
   if (!h) return fail(VB_E_ARG, std::string(what) + ": null handle");
   if (!h->fin) return fail(VB_E_STATE, std::string(what) + " before vb_finalize");
@@ -73,7 +76,6 @@ int checkReportErr(vb_handle h) {
   return 0;
 }
 
-}  // namespace
 }  // namespace viba_host
 
 extern "C" {

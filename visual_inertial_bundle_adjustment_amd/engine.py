@@ -675,6 +675,58 @@ class HipEngine(CEngineBase):
         self._check(self._fn("report_device_ms", [_dp])(self.h, C.byref(ms)))
         return ms.value
 
+    # ---------------------------------------------------------------- non-linearity inspection
+    def factor_expected_delta(self, kind: int, first: int = 0, n: int | None = None, which: int = 0) -> dict:
+        """singleExpectedDelta (Factor.h:470-540) of rows [first, first + n) of `kind` along the step the
+        engine holds (which: 0 step, 1 sub-step; vb_factor_expected_delta): dict of v0 (the cost at the
+        current variables, -1 for a failing factor), delta (the change its linearization predicts) and
+        grad_norm (n each)."""
+        kind, first = int(kind), int(first)
+        if n is None:
+            n = max(0, self.num_factors(kind) - first)
+        n = int(n)
+        v0, delta, gn = (np.zeros(max(n, 0)) for _ in range(3))
+        f = self._fn("factor_expected_delta", [C.c_int, C.c_int64, C.c_int64, C.c_int, P, P, P])
+        self._check(f(self.h, kind, first, n, int(which), v0.ctypes.data, delta.ctypes.data, gn.ctypes.data))
+        return {"v0": v0, "delta": delta, "grad_norm": gn}
+
+    def _inspection(self, fn, *args) -> dict:
+        from .kinds import INSPECT_MAX_K
+        kinds, rows = np.zeros(INSPECT_MAX_K, np.int32), np.zeros(INSPECT_MAX_K, np.int64)
+        score, v0, delta, v1, gn = (np.zeros(INSPECT_MAX_K) for _ in range(5))
+        nf, nc = C.c_int32(), C.c_int64()
+        self._check(fn(self.h, *args, kinds.ctypes.data, rows.ctypes.data, score.ctypes.data, v0.ctypes.data,
+                       delta.ctypes.data, v1.ctypes.data, gn.ctypes.data, C.byref(nf), C.byref(nc)))
+        m = nf.value
+        return {"kind": kinds[:m].copy(), "row": rows[:m].copy(), "score": score[:m].copy(), "v0": v0[:m].copy(),
+                "delta": delta[:m].copy(), "v1": v1[:m].copy(), "grad_norm": gn[:m].copy(), "n_compared": nc.value}
+
+    def inspect_nonlinearities(self, k: int = 5, which: int = 0, kinds=None) -> dict:
+        """The k factors whose cost the step's linear prediction misses most (vb_inspect_nonlinearities;
+        Optimizer.cpp:861-872, 727-766), worst first: dict of kind, row, score, v0, delta, v1, grad_norm
+        (n_found each) and n_compared.  kinds: the factor kinds that take part (None: all 14).  Leaves the
+        step applied and the linearization point in the backup: restore() goes back."""
+        from .kinds import NUM_FACTOR_KINDS
+        mask = (1 << NUM_FACTOR_KINDS) - 1 if kinds is None else sum({1 << int(x) for x in kinds})
+        f = self._fn("inspect_nonlinearities", [C.c_int, C.c_uint32, C.c_int32] + [P] * 9)
+        return self._inspection(f, int(which), mask, int(k))
+
+    def set_inspect_iteration(self, n: int, k: int = 5):
+        """Settings::triggerDebuggingOfNonlinearities: iteration n (1-based; <= 0: off) of the next optimize
+        calls runs inspect_nonlinearities(k) in place of its step and ends the run with a zeroed Summary
+        (vb_set_inspect_iteration); inspection_result() has what it found."""
+        self._check(self._fn("set_inspect_iteration", [C.c_int, C.c_int32])(self.h, int(n), int(k)))
+
+    def inspection_result(self) -> dict:
+        """the last inspection's result (vb_inspection_result), as inspect_nonlinearities returns it"""
+        return self._inspection(self._fn("inspection_result", [P] * 9))
+
+    def inspect_device_ms(self):
+        """device time [ms] of the last inspect_nonlinearities: (x0 pass, x1 pass, selection)"""
+        ms = (C.c_double * 3)()
+        self._check(self._fn("inspect_device_ms", [C.c_double * 3])(self.h, ms))
+        return tuple(ms)
+
     # ---------------------------------------------------------------- calibration against factory
     def calib_projection_offsets(self, factory_cam, factory_T, cam_intr_var, cam_extr_var, fcam_of_pair, weight,
                                  series_of_pair, n_series: int, distances, want_values: bool = False) -> dict:

@@ -40,5 +40,8 @@ ERR_UNWEIGHTED, ERR_WEIGHTED, ERR_ROT_DEG, ERR_VEL_CM_S, ERR_POS_CM = range(5)
 FACTOR_ERROR_SIZE = (2, 9, 9, 9, 3, 23, 17, 6, 6, 6, 23, 17, 6, 6)
 REPORT_MAX_GROUPS, REPORT_MAX_EDGES = 64, 32
 
+# non-linearity inspection (include/viba_hip.h VB_INSPECT_MAX_K): the most factors one call returns
+INSPECT_MAX_K = 64
+
 # reduced-system solvers (include/viba_hip.h VB_SOLVER_*; Optimizer.h:31-37 SolverType)
 SOLVER_DIRECT, SOLVER_PCG_TRIVIAL, SOLVER_PCG_JACOBI, SOLVER_PCG_GAUSS_SEIDEL, SOLVER_PCG_LOWER_PREC = range(5)
