@@ -1,5 +1,5 @@
 """The non-linearity inspection (vb_inspect_nonlinearities, csrc/inspect.hip + the expected-delta kernels of
-csrc/factors.hip) of a synthetic config after one linearization and solve: prints the reference's block of
+csrc/visual.hip / csrc/small.hip) of a synthetic config after one linearization and solve: prints the reference's block of
 the worst factors, and times it -- the wall time of one call, the device times of its x0 pass, x1 pass and
 selection (vb_inspect_device_ms) and, beside them, the same build's vb_bench_kernel(10) (the visual
 linearization: what the x0 pass evaluates, storing a 576 B record where the x0 pass stores 24 B) and

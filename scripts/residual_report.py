@@ -1,6 +1,6 @@
 """The residual report (report.residual_report: vb_error_histogram / vb_factor_errors) of a synthetic config:
 prints it, and times it -- the wall time of the full report, the device time of the visual histogram pass
-(visual_report_kernel, csrc/factors.hip) and, beside it, vb_bench_kernel(15): the visual cost pass of the
+(visual_report_kernel, csrc/visual.hip) and, beside it, vb_bench_kernel(15): the visual cost pass of the
 same build, which does the same evaluation without the binning.
 
     python scripts/residual_report.py [config] [--simple] [--precision fp64|mixed]      (default C)

@@ -1,6 +1,6 @@
 """The non-linearity inspection on the device (vb_factor_expected_delta / vb_inspect_nonlinearities /
-vb_set_inspect_iteration: visual_expected_kernel, small_expected_eval_kernel and small_expected_dot_kernel of
-csrc/factors.hip, the key / selection kernels and the C-ABI of csrc/inspect.hip), for the fp64 and the mixed build.
+vb_set_inspect_iteration: visual_expected_kernel of csrc/visual.hip, small_expected_eval_kernel and small_expected_dot_kernel of
+csrc/small.hip, the key / selection kernels and the C-ABI of csrc/inspect.hip), for the fp64 and the mixed build.
 
 Main input: synth.config("miniB") after parity_util.make_failing (the residual report's): 24,491 factors over
 all 14 kinds, 506 visual factors failing at x0 and 35 more only at x1.  References: the CPU oracle's eval_factor

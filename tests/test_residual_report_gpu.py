@@ -1,5 +1,5 @@
-"""The residual report on the device (vb_factor_errors / vb_error_histogram: visual_report_kernel and
-small_report_kernel of csrc/factors.hip, bin_values_kernel and the C-ABI of csrc/report.hip), for the fp64
+"""The residual report on the device (vb_factor_errors / vb_error_histogram: visual_report_kernel of csrc/visual.hip,
+small_report_kernel of csrc/small.hip, bin_values_kernel and the C-ABI of csrc/report.hip), for the fp64
 and the mixed build.
 
 Main input: synth.config("miniB") after parity_util.make_failing: all 14 kinds, rolling shutter, 23,967

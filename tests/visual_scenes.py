@@ -1,6 +1,7 @@
 """The test scenes of tests/test_visual_reference.py (oracle, CPU) and tests/test_visual_reference_gpu.py
 (HIP engine): one-factor problems at the branch edges of the global-shutter visual factor, the loss cases
-and the micro bundle, with their builders for an engine.  The mathematics they are checked against is
+and the micro bundle, with their builders for an engine, and the mixed-shutter validity scene of
+tests/test_visual_validity_gpu.py.  The mathematics they are checked against is
 tests/hp_reference.py; nothing here computes a reference value of its own."""
 from __future__ import annotations
 
@@ -235,6 +236,70 @@ class MicroBundle:
         n = len(self.obs)
         fv = np.column_stack([self.obs, np.full(n, -1)])
         e.add_factors(F_VISUAL, fv, np.full(n, -1), self.consts)
+        e.finalize()
+        return e
+
+
+# ====================================================================== the validity scene
+class ValidityScene:
+    """200 observations for tests/test_visual_validity_gpu.py: visual_lin_kernel's block of 128 lanes gives
+    one full two-wave block, one full wave and one 8-lane partial wave.  50 points, each seen from 4 rigs;
+    rigs 0, 1 carry the global-shutter camera (Linear, 100 observations) and rigs 2, 3 the rolling-shutter one
+    (Linear with a readout time and an estimated time offset, table 0, one free velocity; 100 observations).
+    Rigs 1 and 3 stand at z = 3.2 looking along +z, so the 12 near points (z in [2, 2.8]) lie behind them: 24
+    observations fail, 12 of each shutter, at a depth below -0.3; the others lie more than 0.5 in front of their
+    camera (asserted on the reference's camera-frame point), so no evaluation can disagree by rounding.  The table
+    spans +-20 ms around the midpoint against a readout of 16 ms and an offset of 1 ms: no lookup is out of
+    range, for a failing observation (measured at the image centre) either."""
+
+    N_POINTS, NEAR = 50, tuple(range(3, 50, 4))
+
+    def __init__(self):
+        rng = np.random.default_rng(20250311)
+        back, front = (0.0, 0.0, 0.0), (0.0, 0.0, -3.2)  # t_bw of a rig at z = 0 / z = 3.2, nearly unrotated
+        self.poses = np.stack([_row_of((0.2, 1.0, -0.1), 0.03, np.add(back, (0.1, 0.02, 0.0))),
+                               _row_of((-0.3, 0.8, 0.4), 0.04, np.add(front, (-0.1, 0.05, 0.0))),
+                               _row_of((0.5, -0.7, 0.2), 0.05, np.add(back, (-0.15, -0.05, 0.0))),
+                               _row_of((0.1, 0.9, 0.3), 0.02, np.add(front, (0.12, -0.03, 0.0)))])
+        self.extrs = np.stack([_row_of((0.1, -0.2, 1.0), 0.04, (0.06, 0.0, 0.01)),
+                               _row_of((-0.2, 0.3, 0.9), 0.07, (-0.06, 0.01, -0.01))])
+        rs_cam = linear_record(est_offset=1)
+        rs_cam[4], rs_cam[5], rs_cam[6] = 1, 0.016, 0.001  # has a readout time; readout 16 ms; offset 1 ms
+        self.cams = np.stack([linear_record(), rs_cam])
+        self.vel = np.array([[0.04, -0.02, 0.03]])
+        z = rng.uniform(4.0, 6.0, self.N_POINTS)
+        z[list(self.NEAR)] = rng.uniform(2.0, 2.8, len(self.NEAR))
+        self.points = np.column_stack([rng.uniform(-0.12, 0.12, self.N_POINTS) * z,
+                                       rng.uniform(-0.09, 0.09, self.N_POINTS) * z, z])
+        # rows (point, pose, extrinsics, intrinsics, velocity) and the table (-1: global shutter)
+        self.obs = np.array([(p, rig, rig // 2, rig // 2, 0 if rig >= 2 else -1)
+                             for p in range(self.N_POINTS) for rig in range(4)])
+        self.table = np.where(self.obs[:, 1] >= 2, 0, -1)
+        self.invalid = np.isin(self.obs[:, 0], self.NEAR) & (self.obs[:, 1] % 2 == 1)
+        consts = []
+        for o, bad in zip(self.obs, self.invalid):
+            a = VisualArgs(self.points[o[0]], self.poses[o[1]], self.extrs[o[2]], self.cams[o[3]], (0, 0, 1, 0, 0, 1))
+            assert (float(point_camera(a)[2]) < -0.3) if bad else (float(point_camera(a)[2]) > 0.5)
+            uv = np.array([320.0, 240.0]) if bad else to_float(projection(a)) + rng.uniform(-0.35, 0.35, 2)
+            consts.append(np.concatenate([uv, SQRT_H.ravel()]))
+        self.consts = np.array(consts)
+        # a coasting rig: identity samples at -20, 0, +20 ms, zero rates between them
+        self.rs_offsets = np.array([0, 3])
+        self.rs_samples = np.array([[0, 0, 0, 1, 0, 0, 0, 0, 0, 0, t] for t in (-0.02, 0.0, 0.02)], float)
+        self.rs_interp = np.zeros((2, 9))
+        self.rs_gravity = np.array([[0.0, -9.81, 0.0]])
+
+    def build(self, engine_cls, **kw):
+        from visual_inertial_bundle_adjustment_amd.kinds import (F_VISUAL, VAR_CAM_EXTR, VAR_CAM_INTR, VAR_POINT,
+                                                                 VAR_POSE, VAR_VEL)
+        e = engine_cls(**kw)
+        e.set_vars(VAR_POINT, self.points)
+        e.set_vars(VAR_POSE, self.poses)
+        e.set_vars(VAR_VEL, self.vel)
+        e.set_vars(VAR_CAM_INTR, self.cams)
+        e.set_vars(VAR_CAM_EXTR, self.extrs)
+        e.set_rs_tables(self.rs_offsets, self.rs_samples, self.rs_interp, self.rs_gravity)
+        e.add_factors(F_VISUAL, self.obs, self.table, self.consts)
         e.finalize()
         return e
 

@@ -1,4 +1,4 @@
-// Host side of the HIP LM engine, shared by its translation units: the kernel launchers (factors.hip /
+// Host side of the HIP LM engine, shared by its translation units: the kernel launchers (visual.hip / small.hip /
 // solver.hip / ...), host helpers, the schedules and the handle.  vb_handle_s is a few groups, one per lifetime:
 // a group's owner (devmem.hpp), the device pointers into its memory and its host-side data are one object, and
 // dropping the object is the only way to undo the group.  Finalized and the lazy groups are built beside the
@@ -27,7 +27,7 @@
 #include "symbolic.hpp"
 
 namespace viba {
-// kernels (factors.hip / solver.hip)
+// kernels (visual.hip / small.hip / refine.hip / lm_kernels.hip / solver.hip)
 void launch_visual_lin(const Dev& d, int updateCache, int dontRetry, int64_t lo, int64_t hi, hipStream_t st);
 void launch_visual_cost(const Dev& d, int comparable, int64_t lo, int64_t hi, hipStream_t st);
 void launch_fold_red(const Dev& d, hipStream_t st);

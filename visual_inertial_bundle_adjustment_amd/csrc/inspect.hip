@@ -5,7 +5,7 @@
 //                                 the factor fails (visual kinds only)
 //   singleCost(i)                 at the stepped variables: the residual report's cost (report.hip)
 //   score                         |v0 + delta - v1| / (min(|grad|, 1000) + 1)
-// The expected-delta kernels are in factors.hip beside the evaluators (inspect.hpp); the stepped costs come
+// The expected-delta kernels are in visual.hip / small.hip beside the evaluators (inspect.hpp); the stepped costs come
 // from the residual report's kernels (so v1 is vb_factor_errors' cost bit for bit); here the score / key
 // kernel, the exact top-k selection and the C-ABI.
 // Items of one inspection: the visual factors by position of obCostOrder (global shutter first, so a wave

@@ -1,5 +1,5 @@
 // Non-linearity inspection (vb_factor_expected_delta / vb_inspect_nonlinearities): what the expected-delta
-// kernels of factors.hip (the factor evaluations live there) and inspect.hip (score, selection, the C-ABI)
+// kernels of visual.hip / small.hip (beside the factor evaluations) and inspect.hip (score, selection, the C-ABI)
 // share.
 #pragma once
 #include "engine.hpp"
@@ -23,7 +23,7 @@ struct InsStage {
   int64_t cap = 0;
 };
 
-// factors.hip
+// visual.hip / small.hip
 // visual kind; err: bit 1 = a rolling-shutter lookup out of range
 void launch_visual_expected(const Dev& d, const int32_t* posOfRow, const InsRows& R, int32_t* err, hipStream_t st);
 // small kinds 1..13, R.n <= S.cap

@@ -6,7 +6,7 @@
 //   covWeightedSquaredError   0.5 e^T P e (P: inverse rvpCov of the inertial kinds, H of the pose prior;
 //                             every other functor whitens its own return: equal to the unweighted one)
 //   singleCost                computeSingleCost(i, false) = 0.5 rho(e^T P e); stored cache untouched
-// The factor evaluations are those of the LM loop (factors.hip: vis_eval / rs_eval of the cost pass,
+// The factor evaluations are those of the LM loop (factor_eval.hpp: vis_obs_eval as the cost pass calls it; small.hip:
 // small_eval's evaluate-only instantiation); here the generic binning kernel of the small kinds and the
 // C-ABI.  The report reads the variables and rolling-shutter tables and writes only buffers of its own:
 // the cost cache, the red[] / error-word slots, the step and the speculative buffers stay as they are.

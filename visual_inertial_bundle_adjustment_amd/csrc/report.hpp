@@ -1,4 +1,4 @@
-// Residual report (vb_factor_errors / vb_error_histogram): what the report kernels of factors.hip (the
+// Residual report (vb_factor_errors / vb_error_histogram): what the report kernels of visual.hip / small.hip (the
 // factor evaluations live there) and report.hip (the generic binning, the C-ABI) share.
 #pragma once
 #include "engine.hpp"
@@ -72,7 +72,7 @@ __device__ __forceinline__ void rep_flush(RepTable& t, const RepHist& H) {
 }
 #endif
 
-// factors.hip
+// visual.hip / small.hip
 // visual kind: rows R of vb_add_factors order (posOfRow: row -> position of obCostOrder) ...
 void launch_visual_rows(const Dev& d, const int32_t* posOfRow, const RepRows& R, int32_t* err, hipStream_t st);
 // ... or the histogram of all observations in obCostOrder (H.grp by position); err: bit 1 = a rolling-

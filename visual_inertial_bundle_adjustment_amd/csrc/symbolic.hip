@@ -409,7 +409,7 @@ Status reducedLayout(const Registration& reg, const Dissection& nd, Layout& lay)
   for (int64_t r = off; r < aligned; r++) lay.padRows.push_back(r);
   lay.rvOff[nRV] = off;
   lay.nRed = off;
-  // the small-factor assembly packs a reduced row with 5 more bits into an int32 (factors.hip)
+  // the small-factor assembly packs a reduced row with 5 more bits into an int32 (small.hip)
   if (lay.nRed >= ((int64_t)1 << 26)) return {VB_E_ARG, "reduced system order must stay below 2^26"};
   lay.nT = (int32_t)((lay.nRed + TS - 1) / TS);
   // owner of every tile column (trailing padding joins the last part).  Parts start on tile boundaries
