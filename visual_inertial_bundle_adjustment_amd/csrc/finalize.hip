@@ -11,6 +11,8 @@ Knobs readKnobs(const vb_handle_s& h) {
   // VIBA_ND_CUTWIN=0: the round-1 order, the median cut with left separators (tests/test_ordering_gpu.py)
   if (const char* e = getenv("VIBA_ND_CUTWIN")) k.cutWin = std::max(0.0, std::min(0.45, atof(e)));
   if (const char* e = getenv("VIBA_ND_LEAF")) k.leafDims = std::max<int64_t>(64, atoll(e));
+  // VIBA_ND_KINDS=0: every part in plain time order, the order before the class order (tests/test_kind_order_gpu.py)
+  if (const char* e = getenv("VIBA_ND_KINDS")) k.kindOrder = atoi(e) != 0;
   k.stats = getenv("VIBA_STATS") != nullptr;
   k.ptFuseMax = h.tune.ptFuseMax, k.useSn = h.tune.useSn, k.snStreams = h.tune.snStreams;
   return k;

@@ -56,6 +56,7 @@ bool precisionChol(const double* cov, int m, double* U);
 struct Knobs {
   double cutWin = 0.05;      // VIBA_ND_CUTWIN: half width of the cut window around a part's median, 0 .. 0.45
   int64_t leafDims = 1024;   // VIBA_ND_LEAF: parts of at most this many dims are not dissected (>= 64)
+  bool kindOrder = true;     // VIBA_ND_KINDS: order every dissection part by variable class (0: plain time order)
   int64_t ptFuseMax = 256;   // column-schedule levels with at most this many off-diagonal tiles are fused
   bool useSn = true;         // VIBA_SUPERNODE: also build the two-column supernode schedules
   int snStreams = 2;         // VIBA_SN_STREAMS: streams of the single-handle supernode schedule, 1 .. 4
