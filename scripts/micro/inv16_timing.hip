@@ -1,4 +1,4 @@
-// Cycle counts of 16 x 16 lower-triangular inverse variants (the second half of solver.hip diag16), one
+// Cycle counts of 16 x 16 lower-triangular inverse variants (the second half of tile_chol.hpp diag16), one
 // wave, clock64() around `iters` calls; every result is summed into a sink so nothing is dead code.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form=1 \
 //     scripts/micro/inv16_timing.hip -o scripts/micro/inv16_timing

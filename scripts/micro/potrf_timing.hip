@@ -1,16 +1,13 @@
-// Cycle counts of the supernode diagonal-block factorization and its 16 x 16 steps (solver.hip potrf_core,
+// Cycle counts of the supernode diagonal-block factorization and its 16 x 16 steps (tile_chol.hpp potrf_core,
 // diag16, Chol16) on a random SPD 128 x 128 block, one workgroup, clock64() around each call.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form=1 \
 //     -I visual_inertial_bundle_adjustment_amd/csrc scripts/micro/potrf_timing.hip -o /tmp/potrf_timing
-#include "../../visual_inertial_bundle_adjustment_amd/csrc/solver.hip"
+#include "../../visual_inertial_bundle_adjustment_amd/csrc/tile_chol.hpp"
 
 #include <cstdio>
 #include <random>
 #include <vector>
 
-namespace viba {
-ProfSlot g_prof;  // (api.hip's; the launch wrappers reference it)
-}
 using namespace viba;
 
 // diag16 alone (one wave), `iters` times on the same S: cycles per call.  Caution: its LDS results are

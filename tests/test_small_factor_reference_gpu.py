@@ -1,5 +1,5 @@
 """The HIP engine's 13 non-visual factor kinds (small_kernel and small_assemble_kernel of csrc/small.hip,
-boxplus_reduced_kernel of csrc/solver.hip, the whitening of csrc/host.hpp and preint_whiten_kernel of
+boxplus_reduced_kernel of csrc/step.hip, the whitening of csrc/host.hpp and preint_whiten_kernel of
 csrc/preint.hip) against the independent 50-digit reference of tests/hp_small_factors.py, on the scenes of
 tests/small_factor_scenes.py, for the fp64 and the mixed build.  The checks are those of
 tests/test_small_factor_reference.py, which holds the CPU oracle to the same reference: cost (linearize and
@@ -17,7 +17,7 @@ covariance 1.9e-11 (the same scenes), variables after the step 9.5e-14; sharp sm
 2.3e-13) cost 1.3e-15, translation gradient 9.4e-16; whitening of the kappa_2 = 1e6 covariance cost 2.8e-13,
 gradient 1.1e-11 against 1.6e-8; recomputed preintegration (preint_whiten_kernel, kappa_2 1.2e3) cost 7.4e-15,
 gradient 9.2e-15; micro bundle (order 164, lambda 1, cond 5.1e4) gradient 3.5e-14, step 2.8e-14, variables
-1.8e-15.  No mismatch: small.hip, solver.hip, host.hpp and preint.hip agree with the reference on every
+1.8e-15.  No mismatch: small.hip, step.hip, host.hpp and preint.hip agree with the reference on every
 scene, so no bound was widened and no kernel changed.
 """
 from __future__ import annotations

@@ -1,5 +1,5 @@
 // Host side of the HIP LM engine, shared by its translation units: the kernel launchers (visual.hip / small.hip /
-// solver.hip / ...), host helpers, the schedules and the handle.  vb_handle_s is a few groups, one per lifetime:
+// chol.hip / ...), host helpers, the schedules and the handle.  vb_handle_s is a few groups, one per lifetime:
 // a group's owner (devmem.hpp), the device pointers into its memory and its host-side data are one object, and
 // dropping the object is the only way to undo the group.  Finalized and the lazy groups are built beside the
 // handle and installed once whole, so a failure leaves the handle as it was.  api.hip: the C-ABI and the queued
@@ -27,15 +27,19 @@
 #include "symbolic.hpp"
 
 namespace viba {
-// kernels (visual.hip / small.hip / refine.hip / lm_kernels.hip / solver.hip)
+// kernel launchers, each group under the file that defines it
+// visual factors (visual.hip)
 void launch_visual_lin(const Dev& d, int updateCache, int dontRetry, int64_t lo, int64_t hi, hipStream_t st);
 void launch_visual_cost(const Dev& d, int comparable, int64_t lo, int64_t hi, hipStream_t st);
+// LM bookkeeping (lm_kernels.hip)
 void launch_fold_red(const Dev& d, hipStream_t st);
 void launch_copy_vars(const Dev& d, bool backup, const int64_t* len, hipStream_t st);
 void launch_spec_commit(const Dev& d, hipStream_t st);
+// small factors (small.hip)
 void launch_small(const Dev& d, int mode, double* gOut, hipStream_t st);
 void launch_small_eval(const Dev& d, int mode, double* gOut, hipStream_t st);
 void launch_small_assemble(const Dev& d, int mode, double* gOut, hipStream_t st, int part = 3);
+// rolling shutter (rs.hip), triangulation (triangulate.hip), preintegration (preint.hip), point refinement (refine.hip)
 void launch_rs_build(const Dev& d, hipStream_t st);
 void launch_rs_row_poses(const Dev& d, int64_t n, const int32_t* obsRig, const int32_t* obsCam, const double* obsRow,
                          const double* rigPose, const double* rigVel, const int32_t* rigRS, const double* cams,
@@ -46,12 +50,14 @@ void launch_triangulate(int64_t nTracks, int64_t nObs, const int64_t* start, con
 void launch_preint(const Dev& d, const PreintArgs& pa, hipStream_t st);
 void launch_refine_points(const Dev& d, const int64_t* gStart, const int32_t* gObs, const int32_t* gPt, int64_t nG,
                           double* backups, double* acc, hipStream_t st);
+// landmark elimination and Schur products (schur.hip)
 void launch_landmark(const Dev& d, double lambda, int mode, int64_t lo, int64_t hi, hipStream_t st);
 void launch_schur(const Dev& d, double lambda, int addIdentity, hipStream_t st);
 void launch_damp(const Dev& d, double lambda, int addIdentity, hipStream_t st);
 void launch_groups(const Dev& d, double lambda, hipStream_t st);
 void launch_schur_products(const Dev& d, double lambda, hipStream_t st);
 void launch_reduced_grad(const Dev& d, int mode, hipStream_t st);
+// tile Cholesky: diagonal blocks and rows of both schedules, diagonal inverses, padding (chol.hip)
 void launch_potrf(const Dev& d, const int32_t* tiles, const int32_t* cols, int n, double* dinv, hipStream_t st,
                   const double* fwdB = nullptr, double* fwdY = nullptr);
 void launch_trsm(const Dev& d, const int32_t* diag, const int32_t* target, const int32_t* cols, int n, const double* dinv,
@@ -65,7 +71,22 @@ void launch_snpotrf_trsm(const Dev& d, const int32_t* items, int n, double* Lscr
                          double* fwdB, double* fwdY);
 void launch_sntrsm(const Dev& d, const int32_t* items, int n, const double* dinv, hipStream_t st, const double* fwdY,
                    double* fwdB);
+void launch_diag_inverse(const Dev& d, const int32_t* cols, int64_t n, double* linv, hipStream_t st);
+void launch_pad_diag(const Dev& d, const int64_t* rows, int64_t n, hipStream_t st);
+// tile Cholesky: fan-in (fanin.hip)
 void launch_fanin(const Dev& d, const int32_t* work, const int32_t* pairs, int n, hipStream_t st);
+// persistent triangular solves (trisolve.hip)
+void launch_solve_fanout(const Dev& d, const int32_t* tasksF, int64_t nF, const int32_t* tasksB, int64_t nB,
+                         const int32_t* expF, const int32_t* expB, const int32_t* colTiles, const int32_t* colRows,
+                         const int32_t* rowTiles, const int32_t* rowCol, const double* linv, double* b, double* y,
+                         double* x, unsigned* flags, int G, hipStream_t st, int phases, const int32_t* pre,
+                         int64_t nPre);
+// back-substitution, vector utilities, applyStep (step.hip)
+void launch_backsub(const Dev& d, int mode, int64_t lo, int64_t hi, const double* xr, double* xp, hipStream_t st);
+void launch_dot(const double* a, const double* b, int64_t n, double* out, hipStream_t st);
+void launch_axpby(double* y, const double* x, double a, double b, int64_t n, hipStream_t st);
+void launch_boxplus(const Dev& d, const double* stepRed, const double* stepPt, hipStream_t st);
+// iterative reduced solve (pcg.hip)
 void launch_tile_symv(const double* tiles, const int32_t* tileList, const int32_t* tileRC, int64_t n, const double* x,
                       double* y, const double* stop, hipStream_t st);
 void launch_jacobi_init(const Dev& d, double* jac, hipStream_t st);
@@ -75,28 +96,20 @@ void launch_pcg_xr(double* x, double* r, const double* p, const double* Ap, cons
 void launch_pcg_p(double* p, double* Ap, const double* z, const double* red, int zrNew, int zr, int64_t n,
                   hipStream_t st);
 void launch_pcg_check(double* red, double r0, double tol, int k, int maxIt, int zrNew, hipStream_t st);
+// shard / partition exchange (multi.hip)
 void launch_tile_gather(const Dev& d, const int32_t* tiles, int64_t n, double* out, hipStream_t st);
 void launch_tile_scatter_add(const Dev& d, const int32_t* tiles, int64_t n, const double* in, hipStream_t st);
-void launch_diag_inverse(const Dev& d, const int32_t* cols, int64_t n, double* linv, hipStream_t st);
 void launch_chunk_copy(double* base, const int32_t* idx, int64_t n, int chunk, double* buf, int mode, hipStream_t st);
-void launch_pad_diag(const Dev& d, const int64_t* rows, int64_t n, hipStream_t st);
-void launch_backsub(const Dev& d, int mode, int64_t lo, int64_t hi, const double* xr, double* xp, hipStream_t st);
-void launch_solve_fanout(const Dev& d, const int32_t* tasksF, int64_t nF, const int32_t* tasksB, int64_t nB,
-                         const int32_t* expF, const int32_t* expB, const int32_t* colTiles, const int32_t* colRows,
-                         const int32_t* rowTiles, const int32_t* rowCol, const double* linv, double* b, double* y,
-                         double* x, unsigned* flags, int G, hipStream_t st, int phases, const int32_t* pre,
-                         int64_t nPre);
-void launch_dot(const double* a, const double* b, int64_t n, double* out, hipStream_t st);
-void launch_axpby(double* y, const double* x, double a, double b, int64_t n, hipStream_t st);
-void launch_boxplus(const Dev& d, const double* stepRed, const double* stepPt, hipStream_t st);
+// selected inversion (selinv.hip), point covariances (pointcov.hip)
 void launch_selinv_level(double* tiles, const int32_t* tileIdx, int32_t nT, const int64_t* colStart,
                          const int32_t* colRows, const int32_t* colTiles, const double* linv, double* U,
                          const int32_t* uItems, int nU, const int32_t* zItems, int nZ, const int32_t* dItems, int nD,
                          hipStream_t st);
 void launch_gather(const double* src, const int64_t* idx, int64_t n, double* out, hipStream_t st);
+void launch_zero_tiles(double* tiles, const int32_t* list, int64_t n, hipStream_t st);
 void launch_pointcov(const Dev& d, const int32_t* items, int64_t nSmall, int64_t nBig, const int32_t* reqLm,
                      const int64_t* xStart, const int32_t* xPc, const int64_t* outOff, double* out, hipStream_t st);
-void launch_zero_tiles(double* tiles, const int32_t* list, int64_t n, hipStream_t st);
+// fp32 preconditioner factor (lowprec.hip)
 void launch_lp_cast(const double* in, float* out, int64_t n, hipStream_t st);
 void launch_lp_uncast(const float* in, double* out, int64_t n, hipStream_t st);
 void launch_lp_damp(float* t32, const int32_t* tileIdx, int32_t nT, const int64_t* rvOff, const int32_t* rvDim,
@@ -151,7 +164,7 @@ using namespace viba_host;
 
 // One tile-Cholesky schedule (factorSeq): per elimination level the potrf / trsm / fan-in work
 // lists (offsets lvP / lvT / lvU), the fan-in contribution pairs it indexes, and the fan-out solve
-// task lists over the same columns (solver.hip fwd/bwd_fanout_kernel).
+// task lists over the same columns (trisolve.hip fwd/bwd_fanout_kernel).
 struct Sched : SchedShape {
   int32_t *ptfD = nullptr, *ptfDiagD = nullptr;
   int32_t *potrfTileD = nullptr, *potrfColD = nullptr, *trsmDiagD = nullptr, *trsmTargetD = nullptr,

@@ -1,5 +1,5 @@
 // Device helpers shared by the Schur-assembly kernels (schur.hip) and the factorization / solves
-// (solver.hip): tile geometry, fp64 MFMA, DPP wave sums, XCD-aware block ids.
+// (chol.hip / fanin.hip / trisolve.hip / step.hip): tile geometry, fp64 MFMA, DPP wave sums, XCD-aware block ids.
 #pragma once
 #include "device_math.hpp"
 #include "engine.hpp"
@@ -31,7 +31,6 @@ constexpr int kAccL4 = 1, kAccR = 4;
 
 __device__ inline int rv_dim(const Dev& d, int r) { return d.rvDim[r]; }
 
-//   mode 1: gradient only into gpNew
 // all-lane sum: within each 16-lane row by DPP (quad swaps, then row rotations by 4 and 8), the four
 // row sums by v_readlane -- VALU-local, no LDS-crossbar ds_bpermute round trips
 template <int kCtrl>

@@ -1,6 +1,32 @@
 // Multi-process building blocks (distributed.py): landmark shards, the partitioned factorization and
 // the deferred (one host read per iteration) mode.
+//   chunk_copy_kernel      gathers / scatters / adds listed tiles or 64-row vector blocks to a packed buffer
 #include "host.hpp"
+
+namespace viba {
+// shard / partition exchange (vb_pack_shard_tiles, vb_add_tiles, vb_part_exchange): one block per
+// listed chunk (a 64 x 64 tile of the tile store, or a 64-row block of a reduced vector);
+// mode 0 gathers base -> buf, 1 scatters buf -> base, 2 adds buf into base
+__global__ void __launch_bounds__(256) chunk_copy_kernel(double* base, const int32_t* idx, int chunk, double* buf,
+                                                         int mode) {
+  double* a = base + (int64_t)idx[blockIdx.x] * chunk;
+  double* b = buf + (int64_t)blockIdx.x * chunk;
+  for (int i = threadIdx.x; i < chunk; i += 256) {
+    if (mode == 0) b[i] = a[i];
+    else if (mode == 1) a[i] = b[i];
+    else a[i] += b[i];
+  }
+}
+void launch_chunk_copy(double* base, const int32_t* idx, int64_t n, int chunk, double* buf, int mode, hipStream_t st) {
+  if (n > 0) hipLaunchKernelGGL(chunk_copy_kernel, dim3((unsigned)n), dim3(256), 0, st, base, idx, chunk, buf, mode);
+}
+void launch_tile_gather(const Dev& d, const int32_t* tiles, int64_t n, double* out, hipStream_t st) {
+  launch_chunk_copy(d.tiles, tiles, n, TS * TS, out, 0, st);
+}
+void launch_tile_scatter_add(const Dev& d, const int32_t* tiles, int64_t n, const double* in, hipStream_t st) {
+  launch_chunk_copy(d.tiles, tiles, n, TS * TS, const_cast<double*>(in), 2, st);
+}
+}  // namespace viba
 
 extern "C" {
 // sharded building blocks (landmark shards).  The host controller

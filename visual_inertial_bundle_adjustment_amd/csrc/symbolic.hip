@@ -752,7 +752,7 @@ void tilePattern(const Input& in, const Layout& lay, const Observations& obs, co
 // ---------------------------------------------------------------- 10. Schur assembly work by target tile
 // (this shard's landmarks and observations)
 namespace {
-// landmark entries by target tile, a tile's in runs of identical (maskI, maskJ) (solver.hip
+// landmark entries by target tile, a tile's in runs of identical (maskI, maskJ) (schur.hip
 // schur_run4_kernel), by landmark within a run; entStart: per tile into ents
 Status tileEntries(const Layout& lay, const Panels& pan, const Shard& shard, const Pattern& pat,
                    std::vector<int64_t>& entStart, std::vector<TileEnt>& ents) {
@@ -1098,7 +1098,7 @@ void fanChunks(int32_t t, const std::vector<int64_t>& start, int64_t chunk, std:
   }
 }
 
-// longest chunks first within each XCD's contiguous range of the launch (solver.hip xcd_block: the
+// longest chunks first within each XCD's contiguous range of the launch (kernel_common.hpp xcd_block: the
 // dispatcher hands them out in order, LPT): +0.9%
 void sortChunksPerXcd(std::vector<int32_t>& fan, size_t first) {
   std::vector<std::array<int32_t, 4>> q((fan.size() / 4) - first);

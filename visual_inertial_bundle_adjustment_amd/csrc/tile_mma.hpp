@@ -2,8 +2,8 @@
 // (selinv.hip: the covariances' selected inversion; lowprec.hip: the fp32 Cholesky preconditioner).
 // Both operands of a product are staged whole (transposed on the way in when the op asks for it), then
 // the four waves of the workgroup take 32 x 32 quadrants of C with the fan-in's register layout
-// (solver.hip fanin_accum / fanin_store).  The LM loop's own factorization keeps its ring-pipelined
-// fan-in (solver.hip); these passes run once per covariance request / per preconditioner build.
+// (fanin.hip fanin_accum / fanin_store).  The LM loop's own factorization keeps its ring-pipelined
+// fan-in (fanin.hip); these passes run once per covariance request / per preconditioner build.
 #pragma once
 #include <hip/hip_runtime.h>
 
