@@ -3,7 +3,7 @@ the CPU oracle (plain loops: no panel classes, chunks or windows).  Every proble
 `one_step` (linearize, damp / factor / solve, apply, comparable cost pass, new-gradient solve, restore) on
 the fp64 build at the fp64 bounds of test_parity_gpu.py (+ gradient_entry_errors < 1e-10, which sees a lost
 or doubled record) and on the mixed build at the bounds of test_mixed_precision_step_tolerance; the chunk
-sizes differ between the two builds (csrc/schur.hip: kLmCh 4 / 6, kGrpChunk 31 / 45).
+sizes differ between the two builds (csrc/landmark.hip: kLmCh 4 / 6, csrc/obs_group.hip: kGrpChunk 31 / 45).
 
   per-column     one landmark panel wider than kLmBigCols = 2048 columns sends the whole wide class to
                  landmark_list_kernel (launch_landmark)
@@ -14,6 +14,9 @@ sizes differ between the two builds (csrc/schur.hip: kLmCh 4 / 6, kGrpChunk 31 /
                  columns, either side of landmark_stage_kernel / landmark_obs_wg_kernel
   group windows  observation groups of exactly 1, 31, 32, 45, 46, 1024 and 1025 records: the chunk edges
                  of both builds and the second kGrpIdx = 1024 window of obs_group_kernel
+  breakdown      the per-column and workgroup problems with their widest landmark NaN: the 3 x 3 block's
+                 breakdown flag through landmark_list_kernel and landmark_obs_wg_kernel (miniB's NaN point in
+                 test_optimize_gpu.py raises it in landmark_stage_kernel)
 
 Each test asserts the counts that pin it to its path before it runs, so a generator change cannot move it
 off silently.  Measured on an MI355X (fp64 | mixed):
@@ -26,6 +29,7 @@ No mismatch and no fault: the per-column path, dead until now, computes what the
 """
 from __future__ import annotations
 
+import copy
 import functools
 import itertools
 
@@ -40,7 +44,7 @@ from visual_inertial_bundle_adjustment_amd.kinds import NUM_VAR_KINDS
 
 pytestmark = pytest.mark.gpu
 
-K_LM_SMALL_COLS, K_LM_BIG_COLS, K_GRP_IDX = 256, 2048, 1024  # csrc/engine.hpp, csrc/schur.hip
+K_LM_SMALL_COLS, K_LM_BIG_COLS, K_GRP_IDX = 256, 2048, 1024  # csrc/engine.hpp, csrc/landmark.hip, csrc/obs_group.hip
 
 
 # ------------------------------------------------------------------ counting, as symbolic.hip does
@@ -261,6 +265,46 @@ def test_workgroup_kernel_with_a_wide_panel(precision):
     print(f"workgroup: {p.summary()}; widest panel {cols.max()} columns, {np.sum(cols > K_LM_SMALL_COLS)} wide landmarks")
     assert K_LM_SMALL_COLS < cols.max() <= K_LM_BIG_COLS
     run_against_oracle("workgroup", p, precision)
+
+
+def assert_breakdown_is_reported(p, precision):
+    """The widest landmark of p (which stays as cached: the NaN goes into a copy) gets NaN coordinates; one
+    linearize, which reports no error (its cost is NaN: the linearization does not reject the point), and one
+    damp_factor_solve, whose elimination of that landmark raises the 3 x 3 breakdown flag: VB_E_NUMERIC and
+    errFromWords' text for bit 2 (tested before the reduced system's bit 8).  The library before the three
+    copies of the 3 x 3 block became one reported exactly this on both problems and both builds."""
+    from visual_inertial_bundle_adjustment_amd.engine import HipEngine, VbError
+    l = int(np.argmax(panel_columns(p)))
+    q = copy.copy(p)
+    q.vars = list(p.vars)
+    q.vars[0] = p.vars[0].copy()
+    q.vars[0][l] = np.nan
+    g = HipEngine(imu_calib_options=p.imu_calib_options, precision=precision)
+    synth.load_into(g, q)
+    cost0 = g.linearize(True, False)
+    with pytest.raises(VbError) as ex:
+        g.damp_factor_solve(1e-5)
+    print(f"landmark {l} NaN [{precision}]: linearize cost {cost0}, damp_factor_solve: {ex.value}; last_error {g.last_error()!r}")
+    assert np.isnan(cost0)
+    assert ex.value.code == -4
+    assert g.last_error() == "landmark 3x3 Cholesky breakdown"
+    assert not np.isnan(p.vars[0]).any()
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_per_column_kernel_reports_a_nan_landmark(precision):
+    """landmark_list_kernel's breakdown flag (the problem and the count of test_per_column_dispatch_above_2048_columns)"""
+    p = wide_problem(260)
+    assert panel_columns(p).max() > K_LM_BIG_COLS
+    assert_breakdown_is_reported(p, precision)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_workgroup_kernel_reports_a_nan_landmark(precision):
+    """landmark_obs_wg_kernel's breakdown flag (the problem and the count of test_workgroup_kernel_with_a_wide_panel)"""
+    p = wide_problem(200)
+    assert K_LM_SMALL_COLS < panel_columns(p).max() <= K_LM_BIG_COLS
+    assert_breakdown_is_reported(p, precision)
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)

@@ -569,7 +569,7 @@ int assembleEnqueue(vb_handle h, double lambda) {
   launch_groups(d, lambda, h->str.st2);
   HIPCHK(hipEventRecord(h->str.evJoin, h->str.st2));
   profBegin(h, KF_LANDMARK);
-  launch_landmark(d, lambda, 0, d.lmB, d.lmE, h->str.st);
+  launch_landmark(d, lambda, 0, h->str.st);
   profEnd(h, KF_LANDMARK);
   HIPCHK(hipMemsetAsync(d.rhs, 0, (size_t)d.nT * TS * sizeof(double), h->str.st));
   HIPCHK(hipStreamWaitEvent(h->str.st, h->str.evJoin, 0));
@@ -631,7 +631,7 @@ int vb_gradient_dot_step(vb_handle h, int dont_retry_failed, double* back_red) {
   forkSmall(h, 1, d.gRedNew);
   visualLinShard(h, h->fin->d, 0, dont_retry_failed);
   joinSmall(h);
-  launch_landmark(d, 0.0, 1, d.lmB, d.lmE, h->str.st);
+  launch_landmark(d, 0.0, 1, h->str.st);
   launch_reduced_grad(d, 0, h->str.st);
   HIPCHK(hipMemsetAsync(d.red + 16, 0, 8 * sizeof(double), h->str.st));
   launch_dot(d.gRedNew, d.stepRed, d.nRed, d.red + 16, h->str.st);
@@ -646,7 +646,7 @@ int vb_gradient_dot_step(vb_handle h, int dont_retry_failed, double* back_red) {
 int vb_solve_with_new_gradient(vb_handle h) {
   if (!h || !h->run.factored) return fail(VB_E_STATE, "vb_solve_with_new_gradient needs a factorization");
   Dev& d = h->fin->d;
-  launch_landmark(d, 0.0, 2, d.lmB, d.lmE, h->str.st);
+  launch_landmark(d, 0.0, 2, h->str.st);
   launch_reduced_grad(d, 1, h->str.st);
   HIPCHK(hipMemcpyAsync(h->fin->rhsWork, d.rhs, (size_t)d.nT * TS * sizeof(double), hipMemcpyDeviceToDevice, h->str.st));
   if (pcgMode(h)) {
@@ -859,7 +859,7 @@ int vb_get_gradient(vb_handle h, int kind, double* out) {
     Dev& d = h->fin->d;
     HIPCHK(hipMemsetAsync(d.gRedNew, 0, (size_t)d.nT * TS * sizeof(double), h->str.st));
     if (smallHere(h, 1)) launch_small(d, 1, d.gRedNew, h->str.st);
-    launch_landmark(d, 0.0, 1, d.lmB, d.lmE, h->str.st);
+    launch_landmark(d, 0.0, 1, h->str.st);
     launch_reduced_grad(d, 0, h->str.st);
     return getPerKind(h, d.gRedNew, d.gpNew, kind, out);
   }

@@ -20,7 +20,7 @@ static int covariancePrologue(vb_handle h, double damping, double* used) {
   for (int attempt = 0;; attempt++) {
     if (int rc = vb_linearize(h, 0, 0, nullptr)) return rc;
     HIPCHK(hipMemsetAsync(d.err, 0, sizeof(int32_t), h->str.st));
-    launch_landmark(d, lam, 0, d.lmB, d.lmE, h->str.st);
+    launch_landmark(d, lam, 0, h->str.st);
     HIPCHK(hipMemsetAsync(d.rhs, 0, (size_t)d.nT * TS * sizeof(double), h->str.st));
     launch_schur(d, lam, 1, h->str.st);
     h->run.factorOnly = true;  // (the fused forward solve would run on a stale right-hand side)

@@ -43,9 +43,7 @@ __device__ __forceinline__ void fanin_issue(const Dev& d, const int32_t* pairs, 
     const int i = wave * kGlds + j, tile = i / (kFanK / 2), cp = i % (kFanK / 2);  // 1 KB = 2 columns each
     const int row = (2 * (lane & 31) - fan_rot(2 * cp + hi)) & 63;
     const double* src = d.tiles + (tile ? ti : tk) * TS * TS + (int64_t)(k0 + 2 * cp + hi) * TS + row;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)(buf + tile * kFanK * TS + cp * 2 * TS),
-                                     16, 0, 0);
+    glds<16>(src, buf + tile * kFanK * TS + cp * 2 * TS);
   }
 }
 

@@ -50,11 +50,13 @@ void launch_triangulate(int64_t nTracks, int64_t nObs, const int64_t* start, con
 void launch_preint(const Dev& d, const PreintArgs& pa, hipStream_t st);
 void launch_refine_points(const Dev& d, const int64_t* gStart, const int32_t* gObs, const int32_t* gPt, int64_t nG,
                           double* backups, double* acc, hipStream_t st);
-// landmark elimination and Schur products (schur.hip)
-void launch_landmark(const Dev& d, double lambda, int mode, int64_t lo, int64_t hi, hipStream_t st);
+// landmark elimination (landmark.hip)
+void launch_landmark(const Dev& d, double lambda, int mode, hipStream_t st);
+// observation-group Gram blocks (obs_group.hip)
+void launch_groups(const Dev& d, double lambda, hipStream_t st, int mode = 0);
+// reduced diagonal damping, Schur products, new reduced RHS (schur.hip)
 void launch_schur(const Dev& d, double lambda, int addIdentity, hipStream_t st);
 void launch_damp(const Dev& d, double lambda, int addIdentity, hipStream_t st);
-void launch_groups(const Dev& d, double lambda, hipStream_t st);
 void launch_schur_products(const Dev& d, double lambda, hipStream_t st);
 void launch_reduced_grad(const Dev& d, int mode, hipStream_t st);
 // tile Cholesky: diagonal blocks and rows of both schedules, diagonal inverses, padding (chol.hip)

@@ -1,5 +1,6 @@
-// Device helpers shared by the Schur-assembly kernels (schur.hip) and the factorization / solves
-// (chol.hip / fanin.hip / trisolve.hip / step.hip): tile geometry, fp64 MFMA, DPP wave sums, XCD-aware block ids.
+// Device helpers shared by the Schur-assembly kernels (landmark.hip / obs_group.hip / schur.hip) and the
+// factorization / solves (chol.hip / fanin.hip / trisolve.hip / step.hip): tile geometry, fp64 MFMA, DPP wave
+// sums, XCD-aware block ids, LDS staging, the landmarks' 3 x 3 Cholesky.
 #pragma once
 #include "device_math.hpp"
 #include "engine.hpp"
@@ -70,5 +71,45 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
 }
 
 static inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+// Staging through LDS: a pointer's LDS address for inline-asm ds_ instructions, and the asynchronous
+// global -> LDS copy of kBytes (16 or 4) per lane (the wave's lanes land consecutively from `lds`)
+constexpr int kRecV = 16 / (int)sizeof(rec_t);  // record elements per 16 B piece
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
+}
+template <int kBytes>
+__device__ __forceinline__ void glds(const void* global, void* lds) {
+  static_assert(kBytes == 16 || kBytes == 4, "the sizes in use");  // (the builtin takes a literal size only)
+  const auto* g = (const __attribute__((address_space(1))) void*)global;
+  auto* s = (__attribute__((address_space(3))) void*)lds;
+  if constexpr (kBytes == 16) __builtin_amdgcn_global_load_lds(g, s, 16, 0, 0);
+  else __builtin_amdgcn_global_load_lds(g, s, 4, 0, 0);
+}
+
+// The lower Cholesky factor of a landmark's damped 3 x 3 block, six doubles at Vchol + 6 l in this order
+struct Chol3 {
+  double l00, l10, l20, l11, l21, l22;
+  static __device__ __forceinline__ Chol3 load(const double* p) { return {p[0], p[1], p[2], p[3], p[4], p[5]}; }
+  __device__ __forceinline__ void store(double* p) const { p[0] = l00, p[1] = l10, p[2] = l20, p[3] = l11, p[4] = l21, p[5] = l22; }
+};
+// of the lower triangle v with its diagonal damped (Optimizer.cpp:136-146: v (1 + lambda) + lambda);
+// ok = every pivot positive (false for a NaN)
+__device__ __forceinline__ Chol3 chol3_damped(double v00, double v10, double v20, double v11, double v21, double v22,
+                                              double lambda, bool& ok) {
+  v00 = v00 * (1.0 + lambda) + lambda, v11 = v11 * (1.0 + lambda) + lambda, v22 = v22 * (1.0 + lambda) + lambda;
+  const double l00 = sqrt(v00), l10 = v10 / l00, l20 = v20 / l00;
+  const double d11 = v11 - l10 * l10, l11 = sqrt(d11), l21 = (v21 - l20 * l10) / l11;
+  const double d22 = v22 - l20 * l20 - l21 * l21, l22 = sqrt(d22);
+  ok = v00 > 0 && d11 > 0 && d22 > 0;
+  return {l00, l10, l20, l11, l21, l22};
+}
+// a = L^-1 a, a = L^-T a
+__device__ __forceinline__ void chol3_fwd(const Chol3& L, double& a0, double& a1, double& a2) {
+  a0 = a0 / L.l00, a1 = (a1 - L.l10 * a0) / L.l11, a2 = (a2 - L.l20 * a0 - L.l21 * a1) / L.l22;
+}
+__device__ __forceinline__ void chol3_bwd(const Chol3& L, double& a0, double& a1, double& a2) {
+  a2 = a2 / L.l22, a1 = (a1 - L.l21 * a2) / L.l11, a0 = (a0 - L.l10 * a1 - L.l20 * a2) / L.l00;
+}
 
 }  // namespace viba

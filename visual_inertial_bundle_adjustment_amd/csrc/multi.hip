@@ -118,7 +118,7 @@ int vb_back_substitute(vb_handle h, double* mcr) { return vb_back_substitute_whi
 int vb_assemble_new_rhs(vb_handle h) {
   if (!h || !h->fin) return fail(VB_E_STATE, "not finalized");
   Dev& d = h->fin->d;
-  launch_landmark(d, 0.0, 2, d.lmB, d.lmE, h->str.st);
+  launch_landmark(d, 0.0, 2, h->str.st);
   launch_reduced_grad(d, 1, h->str.st);
   HIPCHK(hipStreamSynchronize(h->str.st));
   return 0;

@@ -23,7 +23,7 @@
 // source columns i (coalesced where the source's tile is not above the column's).
 //
 // Panel width: narrow panels (<= kLmSmallCols columns) one wave per point, wider ones one workgroup per
-// point, as the elimination splits them (schur.hip).  The source columns are staged in LDS in chunks of
+// point, as the elimination splits them (landmark.hip).  The source columns are staged in LDS in chunks of
 // kChunk columns, so LDS never depends on the panel: a panel wider than the chunk streams through it once
 // per group of target columns.
 #include "kernel_common.hpp"

@@ -34,11 +34,8 @@ __global__ void __launch_bounds__(256) backsub_kernel(Dev d, int mode, int64_t l
   if (lane != 0) return;
   const double* zz = mode ? d.zNew : d.z;
   t0 = zz[l * 3] - t0, t1 = zz[l * 3 + 1] - t1, t2 = zz[l * 3 + 2] - t2;
-  const double* L = d.Vchol + l * 6;
-  const double x2 = t2 / L[5];
-  const double x1 = (t1 - L[4] * x2) / L[3];
-  const double x0 = (t0 - L[1] * x1 - L[2] * x2) / L[0];
-  xp[l * 3] = x0, xp[l * 3 + 1] = x1, xp[l * 3 + 2] = x2;
+  chol3_bwd(Chol3::load(d.Vchol + l * 6), t0, t1, t2);
+  xp[l * 3] = t0, xp[l * 3 + 1] = t1, xp[l * 3 + 2] = t2;
 }
 
 // ------------------------------------------------------------------ vector utilities

@@ -624,7 +624,7 @@ Status shardRanges(const Input& in, const Layout& lay, const std::vector<int>& l
   }
   if (shard.lmEnd < 0) shard.lmBegin = 0, shard.lmEnd = nPts;
   if (shard.lmBegin < 0 || shard.lmEnd > nPts || shard.lmBegin > shard.lmEnd) return {VB_E_ARG, "bad landmark shard range"};
-  // landmark lists by panel width (schur.hip landmark_stage_kernel)
+  // landmark lists by panel width (landmark.hip landmark_stage_kernel)
   std::vector<int32_t> big;
   int64_t bigCols = 0;
   shard.lmList.clear();

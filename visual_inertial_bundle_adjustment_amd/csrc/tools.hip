@@ -148,7 +148,7 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
           launch_visual_lin(d, 0, 0, d.obB, d.obE, h->str.st);
           launch_visual_lin(d, 0, 0, d.fB, d.fE, h->str.st);
           break;
-        case 12: launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->str.st); break;  // landmark elimination
+        case 12: launch_landmark(d, 1e-5, 0, h->str.st); break;  // landmark elimination
         case 13: launch_groups(d, 1e-5, h->str.st); break;                     // observation-group Gram blocks
         case 14: launch_schur_products(d, 1e-5, h->str.st); break;             // Schur tile products
         case 15: launch_visual_cost(d, 1, d.obB, d.obE, h->str.st); break;     // cost pass (visual)
@@ -168,11 +168,11 @@ extern "C" int vb_bench_kernel(vb_handle h, int which, int iters, double* avg_us
           if (which == 20) launch_schur_products(d, 1e-5, h->str.st2);
           else launch_groups(d, 1e-5, h->str.st2);
           HIPCHK(hipEventRecord(h->str.evJoin, h->str.st2));
-          launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->str.st);
+          launch_landmark(d, 1e-5, 0, h->str.st);
           HIPCHK(hipStreamWaitEvent(h->str.st, h->str.evJoin, 0));
           break;
         case 21:
-          launch_landmark(d, 1e-5, 0, d.lmB, d.lmE, h->str.st);
+          launch_landmark(d, 1e-5, 0, h->str.st);
           launch_schur_products(d, 1e-5, h->str.st);
           break;
         // the factorization (its streams) alone (23), and beside the tile products on stF (24); timing only
