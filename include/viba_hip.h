@@ -624,6 +624,45 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
 /* device time [ms] of the last vb_error_histogram's kernels (measurement aid) */
 int vb_report_device_ms(vb_handle h, double* ms);
 
+/* ---------------------------------------------------------------- base-map visual factors
+ * BaseMapVisualFactor (viba/problem/BaseMapVisualFactor.{h,cpp}; added by
+ * MultiSessionProblem::addBaseMapVisualFactor, MultiSessionProblemImpl.h:19-40): a point of the session
+ * observed by a camera of a constant key rig of an existing map.  Its residual and point Jacobian are those of
+ * the global-shutter VisualFactor::operator() (VisualFactor.cpp:49-67) with the pose, extrinsics and camera
+ * held constant, so the base map is a table of the handle and not a 15th factor kind: the key rigs, their
+ * cameras and the factors carry no variables, and only the point block of the system sees them.
+ *   residual   pRig = T_bodyImu_world * X, pCam = T_Cam_BodyImu * pRig; fails when pCam.z < 1e-6;
+ *              e = sqrtH * (projectNoChecks(pCam) - uv)
+ *   Jacobian   J = sqrtH * dProj * R_cb * R_bw   (2 x 3, the point alone)
+ *   loss       the handle's reprojection loss (reprojErrorLoss_)
+ * A camera's estimate flags, readout time and time offset are ignored: the factor is global shutter by
+ * definition.  The ResultCache and CostStats rules are those of the visual kind (Factor.h:390-417, 555-583);
+ * CostStats count the base-map factors.  A constant point's factors add cost and CostStats only.  A free point
+ * with base-map factors and no VB_F_VISUAL row is a landmark with an empty panel;
+ * vb_compute_point_covariances answers VB_E_UNSUPPORTED for it.  vb_refine_points includes a point's base-map
+ * factors (PointRefinement.cpp:30-39).  vb_inspect_nonlinearities and vb_factor_expected_delta leave the
+ * base-map factors out.  On a handle with base-map factors vb_set_landmark_shard, vb_set_partition and
+ * vb_set_deferred return VB_E_UNSUPPORTED, and vb_spec_prepare answers ok = 0 (vb_optimize runs its plain
+ * controller: the same trajectory).
+ * vb_set_basemap and vb_add_basemap_factors precede vb_finalize (VB_E_STATE afterwards); VB_E_ARG for an index
+ * out of range or for factors added before a base map is set; n == 0 succeeds.  vb_set_basemap replaces the
+ * tables (applyWorldTransformation is a host re-upload before vb_finalize) and keeps the factors, whose
+ * camera indices must stay in range. */
+int vb_set_basemap(vb_handle h, int64_t n_keyrigs, const double* T_bodyImu_world7,
+                   int64_t n_cameras, const int32_t* keyrig_of_camera,
+                   const double* T_cam_bodyImu7, const double* cam_data /* VB_CAM_DATA each */);
+int vb_add_basemap_factors(vb_handle h, int64_t n, const int32_t* point, const int32_t* camera,
+                           const double* consts6 /* u, v, sqrtH00, 01, 10, 11 */);
+int vb_num_basemap_factors(vb_handle h, int64_t* n);
+/* The residual report of the base-map factors (Histograms.cpp:72, 257-306), under the rules written above
+ * vb_factor_errors: rows [first, first + n) in vb_add_basemap_factors order, any output NULL; no LM state
+ * changes; VB_E_STATE before vb_finalize.  The histogram is one group. */
+int vb_basemap_errors(vb_handle h, int64_t first, int64_t n, double* raw /* 2 each */,
+                      double* sq_unweighted, double* cost, uint8_t* valid);
+int vb_basemap_histogram(vb_handle h, int which /* VB_ERR_UNWEIGHTED | VB_ERR_WEIGHTED */,
+                         int32_t n_edges, const double* edges, int64_t* counts, double* cost,
+                         int64_t* n_factors, int64_t* n_failing);
+
 /* ---------------------------------------------------------------- non-linearity inspection
  * ark_vi_ba's --trigger-debugging-of-nonlinearities N (Optimizer::Settings::triggerDebuggingOfNonlinearities,
  * lib/small_thing/Optimizer.h:84; read at Optimizer.cpp:861-883 and interfaces/ark/main_AriaKit_ViBa.cpp:103-106):

@@ -609,6 +609,8 @@ def load_into(engine, p: SessionProblem, finalize: bool = True, recompute_preint
     for f in range(kinds.NUM_FACTOR_KINDS):
         if len(p.fivals[f]):
             engine.add_factors(f, p.fvars[f], p.fivals[f], p.fconsts[f])
+    if p.basemap is not None:  # (GeneratedProblem.basemap: the base map's key rigs and factors)
+        p.basemap.load_into(engine)
     for k in (1, 2, 3):
         if len(p.fvars[k]):
             engine.set_preint_sources(k, *p.preint_src[k])

@@ -16,7 +16,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("VIBA_LIB_DIR", os.path.join(HERE, "lib"))
-HIP_SOURCES = ["visual.hip", "small.hip", "refine.hip", "lm_kernels.hip", "landmark.hip", "obs_group.hip", "schur.hip", "chol.hip", "fanin.hip", "trisolve.hip", "step.hip", "rs.hip", "preint.hip", "pcg.hip", "selinv.hip", "lowprec.hip", "api.hip", "factor_host.hip", "pcg_host.hip",
+HIP_SOURCES = ["visual.hip", "basemap.hip", "small.hip", "refine.hip", "lm_kernels.hip", "landmark.hip", "obs_group.hip", "schur.hip", "chol.hip", "fanin.hip", "trisolve.hip", "step.hip", "rs.hip", "preint.hip", "pcg.hip", "selinv.hip", "lowprec.hip", "api.hip", "factor_host.hip", "pcg_host.hip",
                "optimize.hip", "symbolic.hip", "finalize.hip", "covariances.hip", "pointcov.hip", "report.hip", "multi.hip", "tools.hip",
                "triangulate.hip", "calib_eval.hip", "inspect.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -130,6 +130,7 @@ void visualLinShard(vb_handle h, const Dev& d, int updateCache, int dontRetry) {
   launch_visual_lin(d, updateCache, dontRetry, d.obB, d.obE, h->str.st);
   launch_visual_lin(d, updateCache, dontRetry, d.fB, d.fE, h->str.st);
   profEnd(h, KF_VISUAL_LIN);
+  launch_basemap_lin(d, updateCache, dontRetry, h->str.st);
   launch_fold_red(d, h->str.st);
 }
 void visualCostShard(vb_handle h, int comparable) {
@@ -138,6 +139,7 @@ void visualCostShard(vb_handle h, int comparable) {
   launch_visual_cost(d, comparable, d.obB, d.obE, h->str.st);
   launch_visual_cost(d, comparable, d.fB, d.fE, h->str.st);
   profEnd(h, KF_VISUAL_COST);
+  launch_basemap_cost(d, comparable, h->str.st);
   launch_fold_red(d, h->str.st);
 }
 
@@ -229,6 +231,52 @@ int vb_add_factors(vb_handle h, int kind, int64_t n, const int32_t* var_idx, con
   h->prob.fvars[kind].insert(h->prob.fvars[kind].end(), var_idx, var_idx + n * kNumVars[kind]);
   for (int64_t i = 0; i < n; i++) h->prob.fint[kind].push_back(ivals ? ivals[i] : -1);
   h->prob.fconst[kind].insert(h->prob.fconst[kind].end(), consts, consts + n * kNumConsts[kind]);
+  return 0;
+}
+
+// ---- base-map visual factors (BaseMapVisualFactor.{h,cpp}; MultiSessionProblemImpl.h:19-40)
+int vb_set_basemap(vb_handle h, int64_t n_keyrigs, const double* T_bodyImu_world7, int64_t n_cameras,
+                   const int32_t* keyrig_of_camera, const double* T_cam_bodyImu7, const double* cam_data) {
+  if (!h || n_keyrigs < 0 || n_cameras < 0 || (n_keyrigs > 0 && !T_bodyImu_world7) ||
+      (n_cameras > 0 && (!keyrig_of_camera || !T_cam_bodyImu7 || !cam_data)))
+    return fail(VB_E_ARG, "bad vb_set_basemap arguments");
+  if (h->fin) return fail(VB_E_STATE, "vb_set_basemap after vb_finalize");
+  if (n_keyrigs > INT32_MAX || n_cameras > INT32_MAX) return fail(VB_E_ARG, "vb_set_basemap: too many key rigs / cameras");
+  for (int64_t c = 0; c < n_cameras; c++)
+    if (keyrig_of_camera[c] < 0 || keyrig_of_camera[c] >= n_keyrigs) return fail(VB_E_ARG, "vb_set_basemap: camera names an unknown key rig");
+  for (const int32_t c : h->prob.bmCamera)
+    if (c >= n_cameras) return fail(VB_E_ARG, "vb_set_basemap: a base-map factor names a camera outside the new base map");
+  Problem& P = h->prob;
+  P.bmRig.assign(T_bodyImu_world7, T_bodyImu_world7 + n_keyrigs * 7);
+  P.bmCamRig.assign(keyrig_of_camera, keyrig_of_camera + n_cameras);
+  P.bmCamT.assign(T_cam_bodyImu7, T_cam_bodyImu7 + n_cameras * 7);
+  P.bmCam.assign(cam_data, cam_data + n_cameras * VB_CAM_DATA);
+  P.bmSet = true;
+  return 0;
+}
+
+int vb_add_basemap_factors(vb_handle h, int64_t n, const int32_t* point, const int32_t* camera, const double* consts6) {
+  if (!h || n < 0 || (n > 0 && (!point || !camera || !consts6))) return fail(VB_E_ARG, "bad vb_add_basemap_factors arguments");
+  if (h->fin) return fail(VB_E_STATE, "vb_add_basemap_factors after vb_finalize");
+  if (n == 0) return 0;
+  if (!h->prob.bmSet) return fail(VB_E_ARG, "vb_add_basemap_factors before vb_set_basemap");
+  if (h->prob.sharded || h->prob.partSet)
+    return fail(VB_E_UNSUPPORTED, "base-map factors need the whole problem on one handle (no shard / partition)");
+  const int64_t nCam = (int64_t)h->prob.bmCamRig.size();
+  for (int64_t i = 0; i < n; i++) {
+    if (camera[i] < 0 || camera[i] >= nCam) return fail(VB_E_ARG, "vb_add_basemap_factors: camera index out of range");
+    if (point[i] < 0) return fail(VB_E_ARG, "vb_add_basemap_factors: point index out of range");
+  }
+  // (the points are checked against the point variables at vb_finalize, as vb_add_factors' handles are)
+  h->prob.bmPoint.insert(h->prob.bmPoint.end(), point, point + n);
+  h->prob.bmCamera.insert(h->prob.bmCamera.end(), camera, camera + n);
+  h->prob.bmConst.insert(h->prob.bmConst.end(), consts6, consts6 + n * 6);
+  return 0;
+}
+
+int vb_num_basemap_factors(vb_handle h, int64_t* n) {
+  if (!h || !n) return fail(VB_E_ARG, "vb_num_basemap_factors: null argument");
+  *n = (int64_t)h->prob.bmPoint.size();
   return 0;
 }
 
@@ -398,12 +446,17 @@ int vb_refine_points(vb_handle h, double* costs, int64_t* stats) {
     std::vector<int32_t> obPt(d.nObs);
     if (d.nObs) HIPCHK(hipMemcpy(obPt.data(), d.obPt, d.nObs * sizeof(int32_t), hipMemcpyDeviceToHost));
     const int64_t nP = d.nvar[0];
+    // (a point's base-map factors follow its visual ones, as entries -(position + 1): refine_eval)
+    const std::vector<int32_t>& bmRow = h->fin->bmRowOfPos;
+    const int64_t nBm = d.bm.n, nEnt = d.nObs + nBm;
     std::vector<int64_t> cnt(nP + 1, 0);
     for (int32_t p : obPt) cnt[p + 1]++;
+    for (int64_t i = 0; i < nBm; i++) cnt[h->prob.bmPoint[bmRow[i]] + 1]++;
     for (int64_t p = 0; p < nP; p++) cnt[p + 1] += cnt[p];
-    std::vector<int32_t> obs(d.nObs);
+    std::vector<int32_t> obs(nEnt);
     std::vector<int64_t> pos(cnt.begin(), cnt.end() - 1);
     for (int64_t o = 0; o < d.nObs; o++) obs[pos[obPt[o]]++] = (int32_t)o;
+    for (int64_t i = 0; i < nBm; i++) obs[pos[h->prob.bmPoint[bmRow[i]]]++] = (int32_t)(-(i + 1));
     std::vector<int64_t> gs(1, 0);
     std::vector<int32_t> gp;
     for (int64_t p = 0; p < nP; p++)
@@ -412,7 +465,7 @@ int vb_refine_points(vb_handle h, double* costs, int64_t* stats) {
     g->nRefG = (int64_t)gp.size();
     DevOwner& m = g->mem;
     if (m.put(&g->refStartD, gs) || m.put(&g->refObsD, obs) || m.put(&g->refPtD, gp) ||
-        m.zeroed(&g->refBackD, (size_t)d.nObs) || m.zeroed(&g->refAccD, 8))
+        m.zeroed(&g->refBackD, (size_t)nEnt) || m.zeroed(&g->refAccD, 8))
       return devFail(m, "vb_refine_points: device allocation");  // (g goes: the next call starts over)
     h->refine = std::move(g);
   }
@@ -458,6 +511,7 @@ int vb_set_landmark_shard(vb_handle h, int64_t lm_begin, int64_t lm_end, int is_
   if (!h) return fail(VB_E_ARG, "null handle");
   if (h->fin) return fail(VB_E_STATE, "vb_set_landmark_shard must precede vb_finalize");
   if (lm_begin < 0 || lm_begin > lm_end) return fail(VB_E_ARG, "bad landmark range");
+  if (!h->prob.bmPoint.empty()) return fail(VB_E_UNSUPPORTED, "vb_set_landmark_shard on a handle with base-map factors");
   h->prob.lmBegin = lm_begin, h->prob.lmEnd = lm_end, h->prob.isRoot = is_root != 0, h->prob.sharded = true;
   return 0;
 }

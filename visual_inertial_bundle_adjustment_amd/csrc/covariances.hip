@@ -211,6 +211,8 @@ int vb_compute_point_covariances(vb_handle h, double damping, int64_t n, const i
     if (points[q] < 0 || points[q] >= d.nvar[VB_VAR_POINT]) return fail(VB_E_ARG, "point handle out of range");
     if (h->fin->lmOfPoint[points[q]] < 0) return fail(VB_E_ARG, "covariance of a constant point");
     reqLm[q] = h->fin->lmOfPoint[points[q]];
+    if (std::binary_search(h->fin->loneLm.begin(), h->fin->loneLm.end(), reqLm[q]))
+      return fail(VB_E_UNSUPPORTED, "covariance of a point that only base-map factors observe");
   }
   if (nw > 0) {
     std::vector<int64_t> lmBlk(d.nPts + 1);

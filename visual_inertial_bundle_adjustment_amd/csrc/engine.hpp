@@ -130,6 +130,29 @@ struct TileWork {
 #endif
 constexpr int kSchurCh = 24, kSchurTR = VIBA_SCHUR_TR;
 
+// Base-map visual factors (basemap.hip; BaseMapVisualFactor.{h,cpp}): points observed by cameras of constant
+// key rigs.  Factors sorted by landmark (position i; constant-point factors last, from nFree on); every
+// pointer is null on a handle without such factors.
+//   tables   rig[7 r] T_bodyImu_world; camera c: camRig[c], camT[7 c] T_Cam_BodyImu, cam[24 c]
+//   factor   pt[i] point handle, camOf[i], C[6 i] (u, v, sqrtH 2x2), cache[i] (ResultCache)
+//   rec      sqrt(rho') * [e (2) | Jpt (6)] of factor i at rec[8 i], fp64 in both builds
+//   Vg       per landmark l: the factors' V (v00 v10 v20 v11 v21 v22) and g (3) at Vg[9 l], summed by
+//            basemap_sum_kernel in position order (no atomics); zero for a landmark without factors
+struct BaseMapDev {
+  int64_t n = 0, nFree = 0;
+  const double *rig = nullptr, *camT = nullptr, *cam = nullptr, *C = nullptr;
+  const int32_t *camRig = nullptr, *pt = nullptr, *camOf = nullptr;
+  const int32_t* posOfRow = nullptr;  // vb_add_basemap_factors row -> position
+  double *cache = nullptr, *rec = nullptr, *Vg = nullptr;
+  const int64_t* start = nullptr;  // nPts + 1: landmark l's factors are positions [start[l], start[l + 1])
+  const int32_t* lmWith = nullptr;  // the landmarks that have factors
+  int64_t nLmWith = 0;
+  // landmarks with base-map factors and no visual observation (an empty observation range and panel): they
+  // are in no lmList class; landmark_lone_kernel ends their 3 x 3 block
+  const int32_t* lone = nullptr;
+  int64_t nLone = 0;
+};
+
 struct Dev {
   // variables
   double* var[9] = {};
@@ -258,6 +281,7 @@ struct Dev {
   // config
   LossParams reproj, imu;
   ImuIdx jac;
+  BaseMapDev bm;
 };
 
 // partitioned factorization: does this handle assemble into tile column `col`?

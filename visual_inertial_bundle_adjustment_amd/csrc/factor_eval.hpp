@@ -229,4 +229,17 @@ __device__ __forceinline__ bool vis_obs_eval(const Dev& d, const VisObs ob, v3 X
                                    WantJ && (ob.flags & 2) != 0, v, &oor);
 }
 
+// BaseMapVisualFactor::operator() (BaseMapVisualFactor.cpp:15-36) of the base-map factor at sorted position i
+// (engine.hpp BaseMapDev) at point X: the global-shutter evaluation with the key rig's pose, the camera's
+// extrinsics and record as constants -- vis_eval's order is the reference's (T_bodyImu_world * X, then
+// T_Cam_BodyImu, fail below z = 1e-6, sqrtH * (proj - uv), J = sqrtH * dProj * R_cb * R_bw); the camera's
+// estimate flags, readout time and time offset are never read on this path.  Residual in v.e, WantJ: v.Jpt.
+template <bool WantJ>
+__device__ __forceinline__ bool bm_eval(const Dev& d, int64_t i, v3 X, VisOut& v) {
+  const int32_t c = d.bm.camOf[i];
+  const se3 Tbw = se3_load(d.bm.rig + (int64_t)d.bm.camRig[c] * 7);
+  const se3 Tcb = se3_load(d.bm.camT + (int64_t)c * 7);
+  return vis_eval<WantJ, true>(d.bm.C + i * 6, X, Tbw, Tcb, d.bm.cam + (int64_t)c * 24, v);
+}
+
 }  // namespace viba

@@ -81,6 +81,8 @@ void keepResults(Symbolic& A, Finalized& f) {
   f.rowStart = std::move(A.pat.rowStart), f.rowColH = std::move(A.pat.rowCol);
   f.shardTiles = std::move(A.schur.shardTiles);
   if (A.preint.present) f.piNoise = std::move(A.preint.noise);
+  f.bmRowOfPos = std::move(A.bm.rowOfPos);
+  f.loneLm = f.shard.loneList;
 }
 
 // the rolling-shutter tables: rebuilt on the device (capacities from the IMU stream), or as given
@@ -108,6 +110,29 @@ int uploadRsTables(const Problem& P, Finalized& f) {
   if (f.rsOff.empty()) f.rsOff.assign(1, 0);
   if (m.put(&d.rsOff, f.rsOff) || m.put(&d.rsS, P.rsS) || m.put(&d.rsI, P.rsI) || m.put(&d.rsG, P.rsG) ||
       m.put(&d.rsN, cnt))
+    return VB_E_HIP;
+  return 0;
+}
+
+// the base map's tables, its factors gathered in sorted order, their cache, records and per-landmark sums:
+// nothing is allocated on a handle without base-map factors
+int uploadBaseMap(const Problem& P, const Symbolic& A, Finalized& f) {
+  const BaseMapOrder& B = A.bm;
+  if (B.n == 0) return 0;
+  BaseMapDev& b = f.d.bm;
+  DevOwner& m = f.mem;
+  std::vector<int32_t> pt(B.n), cam(B.n);
+  std::vector<double> C((size_t)B.n * 6);
+  for (int64_t i = 0; i < B.n; i++) {
+    const int64_t r = B.rowOfPos[i];
+    pt[i] = P.bmPoint[r], cam[i] = P.bmCamera[r];
+    std::copy(&P.bmConst[r * 6], &P.bmConst[r * 6] + 6, &C[i * 6]);
+  }
+  b.n = B.n, b.nFree = B.nFree, b.nLmWith = (int64_t)B.lmWith.size(), b.nLone = (int64_t)A.shard.loneList.size();
+  if (m.put(&b.rig, P.bmRig) || m.put(&b.camT, P.bmCamT) || m.put(&b.cam, P.bmCam) || m.put(&b.camRig, P.bmCamRig) ||
+      m.put(&b.pt, pt) || m.put(&b.camOf, cam) || m.put(&b.C, C) || m.put(&b.posOfRow, B.posOfRow) ||
+      m.put(&b.start, B.start) || m.put(&b.lmWith, B.lmWith) || m.put(&b.lone, A.shard.loneList) ||
+      m.zeroed(&b.cache, B.n) || m.zeroed(&b.rec, (size_t)B.n * 8) || m.zeroed(&b.Vg, (size_t)A.reg.nPts * 9))
     return VB_E_HIP;
   return 0;
 }
@@ -198,6 +223,7 @@ int uploadAll(const Problem& P, const Symbolic& A, Finalized& f) {
       return VB_E_HIP;
   }
   if (int rc = uploadRsTables(P, f)) return rc;
+  if (int rc = uploadBaseMap(P, A, f)) return rc;
   if (m.zeroed(&d.red, 64) || m.zeroed(&d.redS, 2 * 64 * 8) || m.zeroed(&d.err, 8)) return VB_E_HIP;
   return 0;
 }
@@ -209,7 +235,7 @@ int doFinalize(vb_handle h) {
   const Input in{P.data,     P.cst,     P.fvars,   P.fint,  P.fconst, h->cfg.imu_calib_options,
                  P.nRS,      P.sharded, P.lmBegin, P.lmEnd, P.isRoot, P.partSet,
                  P.partRank, P.partWorld, P.piSrc, P.imuT,  P.imuV,   P.piT,
-                 P.piV,      P.piNoise, readKnobs(*h)};
+                 P.piV,      P.piNoise, readKnobs(*h), &P.bmPoint};
   Symbolic A;
   if (const Status e = analyze(in, A)) return fail(e.code, e.msg);
   // built beside the handle and installed whole: a failure drops f with everything it took, and the handle

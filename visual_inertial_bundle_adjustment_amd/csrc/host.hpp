@@ -31,6 +31,9 @@ namespace viba {
 // visual factors (visual.hip)
 void launch_visual_lin(const Dev& d, int updateCache, int dontRetry, int64_t lo, int64_t hi, hipStream_t st);
 void launch_visual_cost(const Dev& d, int comparable, int64_t lo, int64_t hi, hipStream_t st);
+// base-map visual factors (basemap.hip): linearization + the per-landmark sums, cost pass; nothing without factors
+void launch_basemap_lin(const Dev& d, int updateCache, int dontRetry, hipStream_t st);
+void launch_basemap_cost(const Dev& d, int comparable, hipStream_t st);
 // LM bookkeeping (lm_kernels.hip)
 void launch_fold_red(const Dev& d, hipStream_t st);
 void launch_copy_vars(const Dev& d, bool backup, const int64_t* len, hipStream_t st);
@@ -224,6 +227,11 @@ struct Problem {
   int64_t lmBegin = 0, lmEnd = -1;
   bool sharded = false, isRoot = true, partSet = false;
   int partRank = 0, partWorld = 1;  // world 1 with partSet: one rank factors its subtree and the ROOT
+  // the base map (vb_set_basemap): key rig poses (7 each), per camera its key rig, extrinsics (7) and record
+  // (24); its factors (vb_add_basemap_factors): point handle, camera, 6 constants
+  bool bmSet = false;
+  std::vector<double> bmRig, bmCamT, bmCam, bmConst;
+  std::vector<int32_t> bmCamRig, bmPoint, bmCamera;
 };
 
 // vb_create's streams and events, destroyed last
@@ -323,6 +331,8 @@ struct Finalized {
   std::vector<int32_t> visRowOfPos;  // the visual factor row (vb_add_factors order) at every position of obCostOrder
   std::vector<int64_t> rsOff;        // offsets of the device rolling-shutter tables (capacities when rebuilt there)
   std::vector<double> piNoise;       // 6 per IMU, every IMU of the preintegration sources (device copy: pi.noise)
+  std::vector<int32_t> bmRowOfPos;   // the base-map factor row (vb_add_basemap_factors order) at every sorted position
+  std::vector<int32_t> loneLm;       // landmarks without a visual observation, ascending (Shard::loneList)
   int64_t nParams = 0, order = 0, nClear = 0, nTileEnt = 0, tileFirst = 0, tileCount = 0, nPairs = 0;
   int32_t nLevels = 0;
   int64_t costRsB[2] = {0, 0};  // obCostOrder: where the rolling-shutter observations of [obB, obE), [fB, fE) start

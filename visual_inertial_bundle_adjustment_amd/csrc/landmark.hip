@@ -3,6 +3,9 @@
 //   landmark_stage_kernel one wave per landmark: V = sum Jp^T Jp (damped), g_p, the W panel in LDS,
 //   (_obs_wg, _list, landmark_kernel) 3x3 Cholesky, z = L^-1 g_p, Y = L^-1 W
 //   landmark_z_kernel     zNew = L^-1 gpNew
+//   landmark_lone_kernel  landmarks that only base-map factors see: the 3 x 3 block alone
+// Every path adds the landmark's base-map sums (BaseMapDev::Vg, basemap.hip) to V and g before the damped
+// Cholesky, so damping acts on the full block; nothing is read on a handle without base-map factors.
 #include "kernel_common.hpp"
 
 namespace viba {
@@ -15,6 +18,18 @@ __device__ __forceinline__ void landmark_finish(const Dev& d, int64_t l, const C
   chol3_fwd(L, z0, z1, z2);
   d.z[l * 3] = z0, d.z[l * 3 + 1] = z1, d.z[l * 3 + 2] = z2;
   d.gp[l * 3] = g[0], d.gp[l * 3 + 1] = g[1], d.gp[l * 3 + 2] = g[2];
+}
+// the landmark's base-map factors: V (v00 v10 v20 v11 v21 v22) += Vg[0..6), g += Vg[6..9)
+__device__ __forceinline__ void basemap_add_g(const Dev& d, int64_t l, double* g) {
+  if (!d.bm.Vg) return;
+  const double* b = d.bm.Vg + l * 9;
+  g[0] += b[6], g[1] += b[7], g[2] += b[8];
+}
+__device__ __forceinline__ void basemap_add_v(const Dev& d, int64_t l, double& v00, double& v10, double& v20, double& v11,
+                                              double& v21, double& v22) {
+  if (!d.bm.Vg) return;
+  const double* b = d.bm.Vg + l * 9;
+  v00 += b[0], v10 += b[1], v20 += b[2], v11 += b[3], v21 += b[4], v22 += b[5];
 }
 // Y(:, c) = L^-1 w of panel column c (Y plane-interleaved: plane q of panel column c at Y[3 c + q]), and the
 // same for the columns first, first + stride, ... of a W panel in LDS
@@ -51,12 +66,14 @@ __device__ __forceinline__ void landmark_eliminate(const Dev& d, double lambda, 
     }
   }
   g[0] = wave_sum(g[0]), g[1] = wave_sum(g[1]), g[2] = wave_sum(g[2]);
+  basemap_add_g(d, l, g);
   if (mode == 1) {
     if (lane == 0) d.gpNew[l * 3] = g[0], d.gpNew[l * 3 + 1] = g[1], d.gpNew[l * 3 + 2] = g[2];
     return;
   }
   v00 = wave_sum(v00), v10 = wave_sum(v10), v20 = wave_sum(v20);
   v11 = wave_sum(v11), v21 = wave_sum(v21), v22 = wave_sum(v22);
+  basemap_add_v(d, l, v00, v10, v20, v11, v21, v22);
   bool ok;
   const Chol3 L = chol3_damped(v00, v10, v20, v11, v21, v22, lambda, ok);
   if (lane == 0) landmark_finish(d, l, L, ok, g);
@@ -239,6 +256,7 @@ __global__ void __launch_bounds__(64) landmark_stage_kernel(Dev d, double lambda
   lm_stage_loop(d, o0, n, stg, W, 0, 1, lane, v);
 #pragma unroll
   for (int k = 0; k < 9; k++) v[(k + 6) % 9] = wave_sum(v[(k + 6) % 9]);  // g, then V: the order this kernel was tuned in
+  basemap_add_g(d, l, v + 6), basemap_add_v(d, l, v[0], v[1], v[2], v[3], v[4], v[5]);
   bool ok;
   const Chol3 L = chol3_damped(v[0], v[1], v[2], v[3], v[4], v[5], lambda, ok);
   if (lane == 0) landmark_finish(d, l, L, ok, v + 6);
@@ -274,6 +292,7 @@ __global__ void __launch_bounds__(256) landmark_obs_wg_kernel(Dev d, double lamb
   if (tid == 0) {
 #pragma unroll
     for (int k = 0; k < 9; k++) v[k] = part[0][k] + part[1][k] + part[2][k] + part[3][k];
+    basemap_add_g(d, l, v + 6), basemap_add_v(d, l, v[0], v[1], v[2], v[3], v[4], v[5]);
     bool ok;
     const Chol3 L = chol3_damped(v[0], v[1], v[2], v[3], v[4], v[5], lambda, ok);
     landmark_finish(d, l, L, ok, v + 6);
@@ -288,6 +307,19 @@ __global__ void __launch_bounds__(256) landmark_list_kernel(Dev d, double lambda
   const int64_t li = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (li >= n) return;
   landmark_eliminate(d, lambda, 0, d.lmList[first + li]);
+}
+
+// a landmark with base-map factors and no visual observation (BaseMapDev::lone): V and g are its base-map
+// sums, its panel is empty; one thread per landmark
+__global__ void __launch_bounds__(256) landmark_lone_kernel(Dev d, double lambda) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= d.bm.nLone) return;
+  const int64_t l = d.bm.lone[t];
+  const double* b = d.bm.Vg + l * 9;
+  const double g[3] = {b[6], b[7], b[8]};
+  bool ok;
+  const Chol3 L = chol3_damped(b[0], b[1], b[2], b[3], b[4], b[5], lambda, ok);
+  landmark_finish(d, l, L, ok, g);
 }
 
 // mode 2: zNew = L^-1 gpNew, one thread per landmark
@@ -319,6 +351,7 @@ void launch_landmark(const Dev& d, double lambda, int mode, hipStream_t st) {
               d.nLmSmall);
     else if (d.nLmBig)
       launchK(landmark_list_kernel, dim3(blocks(d.nLmBig, 4)), dim3(256), 0, st, d, lambda, d.nLmSmall, d.nLmBig);
+    if (d.bm.nLone) hipLaunchKernelGGL(landmark_lone_kernel, dim3(blocks(d.bm.nLone, 256)), dim3(256), 0, st, d, lambda);
   }
 }
 }  // namespace viba

@@ -130,6 +130,7 @@ int vb_set_partition(vb_handle h, int rank, int world) {
   if (h->fin) return fail(VB_E_STATE, "vb_set_partition must precede vb_finalize");
   if (world < 1 || world > 64 || (world & (world - 1)) || rank < 0 || rank >= world)
     return fail(VB_E_ARG, "vb_set_partition: world must be a power of two in [1, 64], 0 <= rank < world");
+  if (!h->prob.bmPoint.empty()) return fail(VB_E_UNSUPPORTED, "vb_set_partition on a handle with base-map factors");
   h->prob.partRank = rank, h->prob.partWorld = world, h->prob.partSet = true;
   return 0;
 }
@@ -181,6 +182,7 @@ int vb_part_exchange(vb_handle h, int what, int dir, double** buf, int64_t* len)
 // reduction slots, which the caller all-reduces in place on the handle's stream (RCCL) and reads once.
 int vb_set_deferred(vb_handle h, int on) {
   if (!h || !h->fin) return fail(VB_E_STATE, "vb_set_deferred before vb_finalize");
+  if (h->fin->d.bm.n > 0) return fail(VB_E_UNSUPPORTED, "vb_set_deferred on a handle with base-map factors");
   h->run.deferred = on != 0;
   return 0;
 }

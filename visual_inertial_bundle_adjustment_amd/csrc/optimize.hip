@@ -14,6 +14,9 @@ extern "C" {
 bool specPrepare(vb_handle h) {
   if (h->spec) return true;
   const Dev& d = h->fin->d;
+  // base-map factors keep one cost cache and no spare one: no speculation (the plain controller takes the
+  // same decisions, so the trajectory is the same)
+  if (d.bm.n > 0) return false;
   auto s = std::make_unique<SpecState>();
   DevOwner& m = s->mem;
   bool ok = !m.zeroed(&s->tilesAlt, (size_t)d.nTiles * TS * TS) && !m.zeroed(&s->cacheAlt, d.nObs) &&

@@ -1,8 +1,8 @@
 // Point refinement (gfx950): refine_points_kernel and its launcher.
 // refinePoints (viba/problem/PointRefinement.cpp:91-196): per point a few damped Gauss-Newton steps on
 // its visual factors alone, before the LM loop (ark_vi_ba, main_AriaKit_ViBa.cpp:69).  One wave per
-// point (group g: observations gObs[gStart[g] .. gStart[g + 1]) of point variable gPt[g]), lanes over
-// the observations; backups[] holds pointGradHess's costBackups (PointRefinement.cpp:48-75) per slot.
+// point (group g: observations gObs[gStart[g] .. gStart[g + 1]) of point variable gPt[g], its base-map
+// factors after its visual ones), lanes over the observations; backups[] holds pointGradHess's costBackups (PointRefinement.cpp:48-75) per slot.
 // acc[0..4] += start cost, end cost, failures, successful iterations, points with >= 1 iteration.
 #include "factor_eval.hpp"
 
@@ -10,8 +10,11 @@ namespace viba {
 
 // observation o (an id, not a position of obCostOrder: the unpacked index arrays) at the trial point X:
 // whitened residual (and 2x3 point Jacobian); false if the factor fails
+// a negative entry -(i + 1) is the base-map factor at sorted position i (PointRefinement.cpp:30-39: the point's
+// BaseMapVisualFactor rows refine it too, with backups of their own)
 template <bool WantJ>
 __device__ bool refine_eval(const Dev& d, int32_t o, v3 X, VisOut& v) {
+  if (o < 0) return bm_eval<WantJ>(d, -(int64_t)o - 1, X, v);
   const VisObs ob{o, d.obPt[o], d.obPose[o], d.obExtr[o], d.obIntr[o], d.obRS[o], d.obVel[o], 0, d.obC + (int64_t)o * 6};
   bool oor = false;
   const bool ok = vis_obs_eval<WantJ, true>(d, ob, X, v, oor);

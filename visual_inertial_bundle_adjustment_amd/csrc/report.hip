@@ -183,6 +183,64 @@ int vb_error_histogram(vb_handle h, int kind, int which, int32_t n_groups, const
   return 0;
 }
 
+// the base-map factors' report (Histograms.cpp:72, 257-306), under vb_factor_errors' rules
+int vb_basemap_errors(vb_handle h, int64_t first, int64_t n, double* raw, double* sq_unweighted, double* cost,
+                      uint8_t* valid) {
+  if (int rc = reportCommon(h, "vb_basemap_errors")) return rc;
+  const int64_t N = h->fin->d.bm.n;
+  if (first < 0 || n < 0 || first > N || n > N - first) return fail(VB_E_ARG, "vb_basemap_errors: rows out of range");
+  if (n == 0) return 0;
+  DevOwner S;  // frees its buffers when the call returns, on every path
+  RepRows R;
+  R.first = first, R.n = n;
+  if ((raw && S.get(&R.raw, (size_t)n * 2)) || (sq_unweighted && S.get(&R.squ, n)) || (cost && S.get(&R.cost, n)) ||
+      (valid && S.get(&R.valid, n)))
+    return devFail(S, "vb_basemap_errors: device allocation");
+  launch_basemap_rows(h->fin->d, R, h->str.st);
+  HIPCHK(hipGetLastError());
+  if (download(raw, R.raw, (size_t)n * 2, h->str.st) || download(sq_unweighted, R.squ, n, h->str.st) ||
+      download(cost, R.cost, n, h->str.st) || download(valid, R.valid, n, h->str.st))
+    return VB_E_HIP;
+  HIPCHK(hipStreamSynchronize(h->str.st));
+  return 0;
+}
+
+int vb_basemap_histogram(vb_handle h, int which, int32_t n_edges, const double* edges, int64_t* counts, double* cost,
+                         int64_t* n_factors, int64_t* n_failing) {
+  if (int rc = reportCommon(h, "vb_basemap_histogram")) return rc;
+  if (which != VB_ERR_UNWEIGHTED && which != VB_ERR_WEIGHTED) return fail(VB_E_ARG, "vb_basemap_histogram: bad error selector");
+  if (n_edges < 1 || n_edges > VB_REPORT_MAX_EDGES || !edges) return fail(VB_E_ARG, "vb_basemap_histogram: n_edges must be in [1, 32]");
+  for (int32_t e = 0; e < n_edges; e++)
+    if (!std::isfinite(edges[e]) || (e > 0 && !(edges[e] > edges[e - 1])))
+      return fail(VB_E_ARG, "vb_basemap_histogram: edges must be finite and strictly increasing");
+  const size_t nb = (size_t)n_edges + 1;
+  DevOwner S;
+  RepHist H;
+  H.which = which, H.nGroups = 1, H.nEdges = n_edges;
+  double* edgesD = nullptr;
+  if (S.get(&edgesD, n_edges) || S.get(&H.counts, nb) || S.get(&H.cost, 1) || S.get(&H.nFactors, 1) || S.get(&H.nFailing, 1))
+    return devFail(S, "vb_basemap_histogram: device allocation");
+  H.edges = edgesD;
+  hipStream_t st = h->str.st;
+  HIPCHK(hipMemcpyAsync(edgesD, edges, n_edges * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(H.counts, 0, nb * sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(H.cost, 0, sizeof(double), st));
+  HIPCHK(hipMemsetAsync(H.nFactors, 0, sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(H.nFailing, 0, sizeof(unsigned long long), st));
+  launch_basemap_hist(h->fin->d, H, h->tune.numCUs * 8, st);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned long long> cnt(nb);
+  unsigned long long nf = 0, nx = 0;
+  if (download(cnt.data(), H.counts, nb, st) || download(&nf, H.nFactors, 1, st) || download(&nx, H.nFailing, 1, st) ||
+      download(cost, H.cost, 1, st))
+    return VB_E_HIP;
+  HIPCHK(hipStreamSynchronize(st));
+  if (counts) std::copy(cnt.begin(), cnt.end(), counts);
+  if (n_factors) *n_factors = (int64_t)nf;
+  if (n_failing) *n_failing = (int64_t)nx;
+  return 0;
+}
+
 int vb_report_device_ms(vb_handle h, double* ms) {
   if (!h || !ms) return fail(VB_E_ARG, "vb_report_device_ms: null argument");
   *ms = h->rep ? h->rep->histMs : 0.0;

@@ -80,5 +80,9 @@ void launch_visual_rows(const Dev& d, const int32_t* posOfRow, const RepRows& R,
 void launch_visual_hist(const Dev& d, const RepHist& H, int32_t* err, int blocks, hipStream_t st);
 // small kinds 1..13: rows R of kind fk (R.valid is not written: they never fail)
 void launch_small_rows(const Dev& d, int fk, const RepRows& R, hipStream_t st);
+// basemap.hip: rows R of vb_add_basemap_factors order (R.sqw is not written: equal to R.squ), or the one-group
+// histogram of all base-map factors
+void launch_basemap_rows(const Dev& d, const RepRows& R, hipStream_t st);
+void launch_basemap_hist(const Dev& d, const RepHist& H, int blocks, hipStream_t st);
 
 }  // namespace viba

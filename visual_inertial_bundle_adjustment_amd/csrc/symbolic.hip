@@ -140,6 +140,13 @@ Status registerVariables(const Input& in, Registration& reg) {
         }
       }
   }
+  // a free point that a base-map factor names is a landmark too (with no visual row: an empty observation
+  // range, numbered after the observed ones)
+  if (in.bmPoint)
+    for (const int32_t hh : *in.bmPoint) {
+      if (hh < 0 || hh >= reg.nvar[0]) return {VB_E_ARG, "base-map factor references an unknown point"};
+      if (!in.cst[0][hh] && lmOf[hh] < 0) lmOf[hh] = -2;
+    }
   // landmark numbering: by the earliest rig that observes the point (time-banded landmark shards
   // and locality of the Schur lists), ties by handle
   reg.nPts = 0;
@@ -627,8 +634,12 @@ Status shardRanges(const Input& in, const Layout& lay, const std::vector<int>& l
   // landmark lists by panel width (landmark.hip landmark_stage_kernel)
   std::vector<int32_t> big;
   int64_t bigCols = 0;
-  shard.lmList.clear();
+  shard.lmList.clear(), shard.loneList.clear();
   for (int64_t l = shard.lmBegin; l < shard.lmEnd; l++) {
+    if (obs.lmObs[l + 1] == obs.lmObs[l]) {  // only base-map factors see it
+      shard.loneList.push_back((int32_t)l);
+      continue;
+    }
     const int64_t nc = (pan.lmY[l + 1] - pan.lmY[l]) / 3;
     if (nc <= kLmSmallCols) shard.lmList.push_back((int32_t)l);
     else big.push_back((int32_t)l), bigCols = std::max(bigCols, nc);
@@ -1589,6 +1600,34 @@ void costOrder(const Layout& lay, const Observations& obs, const Shard& shard, C
   }
 }
 
+// ---------------------------------------------------------------- 17. base-map factors by landmark
+Status baseMapOrder(const Input& in, const Registration& reg, BaseMapOrder& bm) {
+  bm = BaseMapOrder();
+  if (!in.bmPoint || in.bmPoint->empty()) return {};
+  const std::vector<int32_t>& pt = *in.bmPoint;
+  const int64_t n = (int64_t)pt.size(), nPts = reg.nPts;
+  if (n >= INT32_MAX) return {VB_E_ARG, "too many base-map factors (2^31)"};
+  bm.n = n;
+  bm.start.assign(nPts + 1, 0);
+  for (int64_t r = 0; r < n; r++) {
+    const int32_t l = reg.lmOfPoint[pt[r]];
+    if (l >= 0) bm.start[l + 1]++, bm.nFree++;
+  }
+  for (int64_t l = 0; l < nPts; l++) {
+    if (bm.start[l + 1]) bm.lmWith.push_back((int32_t)l);
+    bm.start[l + 1] += bm.start[l];
+  }
+  bm.rowOfPos.assign(n, 0), bm.posOfRow.assign(n, 0);
+  std::vector<int64_t> fill(bm.start.begin(), bm.start.end() - 1);
+  int64_t tail = bm.nFree;
+  for (int64_t r = 0; r < n; r++) {
+    const int32_t l = reg.lmOfPoint[pt[r]];
+    const int64_t p = l >= 0 ? fill[l]++ : tail++;
+    bm.rowOfPos[p] = (int32_t)r, bm.posOfRow[r] = (int32_t)p;
+  }
+  return {};
+}
+
 // ---------------------------------------------------------------- all stages
 Status analyze(const Input& in, Symbolic& S) {
   if (Status e = registerVariables(in, S.reg)) return e;
@@ -1623,6 +1662,9 @@ Status analyze(const Input& in, Symbolic& S) {
   if (Status e = smallConstants(in, S.small)) return e;
   if (Status e = preintInputs(in, S.preint)) return e;
   costOrder(S.lay, S.obs, S.shard, S.cost);
+  if (in.bmPoint && !in.bmPoint->empty() && (in.partSet || in.sharded))
+    return {VB_E_UNSUPPORTED, "base-map factors need the whole problem on one handle (no shard / partition)"};
+  if (Status e = baseMapOrder(in, S.reg, S.bm)) return e;
   return {};
 }
 

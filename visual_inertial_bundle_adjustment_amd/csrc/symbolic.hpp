@@ -86,6 +86,8 @@ struct Input {
   const std::vector<std::vector<double>>& piV;
   const std::vector<double>& piNoise;
   Knobs knobs;
+  // base-map visual factors (vb_add_basemap_factors): the point handle of every row; nullptr: none
+  const std::vector<int32_t>* bmPoint = nullptr;
 };
 
 // error of a stage: code 0 is success; the caller hands (code, msg) to fail()
@@ -156,6 +158,9 @@ struct Shard {
   std::vector<int32_t> lmList;  // narrow panels (<= kLmSmallCols columns) first, then the wide ones
   int64_t nLmSmall = 0, nLmBig = 0;
   int32_t lmBigCols = 0;
+  // landmarks without a visual observation (free points that only base-map factors name): an empty
+  // observation range and panel, kept out of lmList so no record-staging kernel meets one
+  std::vector<int32_t> loneList;
 };
 // 9. tile pattern with fill, by column and by row
 struct Pattern {
@@ -251,6 +256,16 @@ struct CostOrder {
   int64_t rsBegin[2] = {0, 0};
 };
 
+// 17. base-map factors sorted by landmark, constant-point factors after them (rows keep their order
+// inside a landmark)
+struct BaseMapOrder {
+  int64_t n = 0, nFree = 0;
+  std::vector<int64_t> start;      // nPts + 1: landmark l's factors are positions [start[l], start[l + 1])
+  std::vector<int32_t> rowOfPos;   // position -> vb_add_basemap_factors row
+  std::vector<int32_t> posOfRow;   // and back (the report's order)
+  std::vector<int32_t> lmWith;     // landmarks that have factors, ascending
+};
+
 struct Symbolic {
   Registration reg;
   TimeOrder time;
@@ -268,6 +283,7 @@ struct Symbolic {
   SmallConsts small;
   PreintInputs preint;
   CostOrder cost;
+  BaseMapOrder bm;
 };
 
 // ---------------------------------------------------------------- the stages
@@ -293,6 +309,7 @@ void partitionSets(const Layout& lay, const Pattern& pat, int rank, int world, P
 Status smallConstants(const Input& in, SmallConsts& small);
 Status preintInputs(const Input& in, PreintInputs& preint);
 void costOrder(const Layout& lay, const Observations& obs, const Shard& shard, CostOrder& cost);
+Status baseMapOrder(const Input& in, const Registration& reg, BaseMapOrder& bm);
 
 // all of them in order
 Status analyze(const Input& in, Symbolic& S);

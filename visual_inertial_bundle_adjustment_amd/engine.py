@@ -669,6 +669,60 @@ class HipEngine(CEngineBase):
                       e.ctypes.data, counts.ctypes.data, cost.ctypes.data, nf.ctypes.data, nx.ctypes.data))
         return {"counts": counts, "cost": cost, "n_factors": nf, "n_failing": nx}
 
+    # ---------------------------------------------------------------- base-map visual factors
+    def set_basemap(self, basemap=None, *, T_bodyimu_world=None, keyrig_of_camera=None, T_cam_bodyimu=None, cams=None):
+        """The base map's constant key rigs and cameras (vb_set_basemap; BaseMapVisualFactor.h): a
+        :class:`BaseMap`, or its four arrays -- key rig poses (n, 7), per camera its key rig, T_Cam_BodyImu
+        (m, 7) and camera record (m, 24).  Before finalize; a second call replaces the tables."""
+        if basemap is not None:
+            T_bodyimu_world, keyrig_of_camera = basemap.T_bodyimu_world, basemap.keyrig_of_camera
+            T_cam_bodyimu, cams = basemap.T_cam_bodyimu, basemap.cams
+        rig = _arr(T_bodyimu_world, np.float64).reshape(-1, 7)
+        kr = _arr(keyrig_of_camera, np.int32).reshape(-1)
+        ct, cd = _arr(T_cam_bodyimu, np.float64).reshape(-1, 7), _arr(cams, np.float64).reshape(-1, 24)
+        if not len(kr) == len(ct) == len(cd):
+            raise ValueError("set_basemap: one key rig, T_cam_bodyimu row and camera record per camera")
+        f = self._fn("set_basemap", [C.c_int64, P, C.c_int64, P, P, P])
+        self._check(f(self.h, len(rig), rig.ctypes.data, len(kr), kr.ctypes.data, ct.ctypes.data, cd.ctypes.data))
+
+    def add_basemap_factors(self, point, camera, consts):
+        """Base-map factors (vb_add_basemap_factors; MultiSessionProblem::addBaseMapVisualFactor): point
+        handle, camera of the base map and (u, v, sqrtH00, 01, 10, 11) per row."""
+        pt, cam = _arr(point, np.int32).reshape(-1), _arr(camera, np.int32).reshape(-1)
+        cs = _arr(consts, np.float64).reshape(-1, 6)
+        if not len(pt) == len(cam) == len(cs):
+            raise ValueError("add_basemap_factors: one point, camera and 6 constants per factor")
+        f = self._fn("add_basemap_factors", [C.c_int64, P, P, P])
+        self._check(f(self.h, len(pt), pt.ctypes.data, cam.ctypes.data, cs.ctypes.data))
+
+    def num_basemap_factors(self) -> int:
+        n = C.c_int64()
+        self._check(self._fn("num_basemap_factors", [C.POINTER(C.c_int64)])(self.h, C.byref(n)))
+        return n.value
+
+    def basemap_errors(self, first: int = 0, n: int | None = None) -> dict:
+        """Per-factor errors of base-map rows [first, first + n) in add_basemap_factors order
+        (vb_basemap_errors): dict of raw (n, 2), sq_unweighted, sq_weighted (equal: the functor whitens its
+        return), cost (n) and valid (n, bool), as factor_errors gives them for the visual kind."""
+        first = int(first)
+        n = max(0, self.num_basemap_factors() - first) if n is None else int(n)
+        raw, valid = np.zeros((max(n, 0), 2)), np.zeros(max(n, 0), np.uint8)
+        squ, cost = np.zeros(max(n, 0)), np.zeros(max(n, 0))
+        f = self._fn("basemap_errors", [C.c_int64, C.c_int64, P, P, P, P])
+        self._check(f(self.h, first, n, raw.ctypes.data, squ.ctypes.data, cost.ctypes.data, valid.ctypes.data))
+        return {"raw": raw, "sq_unweighted": squ, "sq_weighted": squ.copy(), "cost": cost, "valid": valid.astype(bool)}
+
+    def basemap_histogram(self, which: int, edges) -> dict:
+        """Histogram of one error (kinds.ERR_UNWEIGHTED / ERR_WEIGHTED) of every base-map factor, one group
+        (vb_basemap_histogram; Histograms.cpp:257-306): counts (len(edges) + 1), cost, n_factors, n_failing."""
+        e = _arr(edges, np.float64).reshape(-1)
+        counts = np.zeros(len(e) + 1, np.int64)
+        cost, nf, nx = C.c_double(), C.c_int64(), C.c_int64()
+        f = self._fn("basemap_histogram", [C.c_int, C.c_int32, P, P, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
+        self._check(f(self.h, int(which), len(e), e.ctypes.data, counts.ctypes.data, C.byref(cost), C.byref(nf),
+                      C.byref(nx)))
+        return {"counts": counts, "cost": cost.value, "n_factors": nf.value, "n_failing": nx.value}
+
     def report_device_ms(self) -> float:
         """device time [ms] of the last error_histogram's kernels (vb_report_device_ms)"""
         ms = C.c_double()

@@ -194,7 +194,17 @@ class ArraySource:
     """``factor_errors`` / ``error_histogram`` / ``num_factors`` of an engine, answered from per-factor arrays:
     per kind a dict of raw (n, m), sq_unweighted, sq_weighted, cost (n) and valid (n)."""
 
-    def __init__(self, per_kind: dict):
+    def __init__(self, per_kind: dict, basemap: dict | None = None):
+        """basemap: the same arrays for the base-map factors (sq_weighted defaults to sq_unweighted), answering
+        num_basemap_factors / basemap_errors / basemap_histogram"""
+        self.basemap = None
+        if basemap is not None:
+            n = len(basemap["cost"])
+            squ = np.asarray(basemap["sq_unweighted"], float)
+            self.basemap = {"raw": np.asarray(basemap["raw"], float).reshape(n, -1), "sq_unweighted": squ,
+                            "sq_weighted": np.asarray(basemap.get("sq_weighted", squ), float),
+                            "cost": np.asarray(basemap["cost"], float),
+                            "valid": np.asarray(basemap.get("valid", np.ones(n)), bool)}
         self.per_kind = {}
         for k, e in per_kind.items():
             n = len(e["cost"])
@@ -213,6 +223,20 @@ class ArraySource:
                     "valid": np.zeros(0, bool)}
         end = None if n is None else first + n
         return {k: v[first:end] for k, v in self.per_kind[kind].items()}
+
+    def num_basemap_factors(self) -> int:
+        return 0 if self.basemap is None else len(self.basemap["cost"])
+
+    def basemap_errors(self, first: int = 0, n: int | None = None) -> dict:
+        end = None if n is None else first + n
+        return {k: v[first:end] for k, v in self.basemap.items()}
+
+    def basemap_histogram(self, which: int, edges) -> dict:
+        e, ok = self.basemap, self.basemap["valid"]
+        v = error_values(e, which)[ok]
+        counts = np.bincount(np.searchsorted(np.asarray(edges, float), v, side="right"), minlength=len(edges) + 1)
+        return {"counts": counts.astype(np.int64), "cost": float(_seq_sum(e["cost"][ok])), "n_factors": len(ok),
+                "n_failing": int((~ok).sum())}
 
     def error_histogram(self, kind: int, which: int, edges, groups=None, n_groups: int = 1) -> dict:
         e = self.factor_errors(kind)
@@ -292,7 +316,8 @@ def _collect(engine, kinds, which, hist, groups):
 
 def residual_report(engine, simple_stats: bool = False, groups=None) -> Report:
     """Histograms::show() (Histograms.cpp:46-137) of the factors `engine` holds, at its current variables.
-    Sections in the reference's order: visual; inertial (main / secondary, or "all inertial"); random walks;
+    Sections in the reference's order: visual (then "Base map factors", Histograms.cpp:257-306, one group, when
+    the engine holds base-map factors); inertial (main / secondary, or "all inertial"); random walks;
     omega priors; factory-calib priors.  simple_stats sets the four switches of SingleSessionProblem.cpp:
     512-521: no pixel histogram, no rotation / velocity / position part, main and secondary inertial merged,
     one aggregate histogram for the random walks and one for the factory-calib priors.  groups: {factor kind:
@@ -318,6 +343,23 @@ def residual_report(engine, simple_stats: bool = False, groups=None) -> Report:
                 hists["pixel"] = pix[g]
             sections.append(Section("visual", "visual factors", label, (F_VISUAL,), int(nf[g]), int(nx[g]), float(cost[g]),
                                     hists, {}, text))
+        # the base map's factors, one group, inside showHistogramsVisual (Histograms.cpp:257-306)
+        n_bm = engine.num_basemap_factors() if hasattr(engine, "num_basemap_factors") else 0
+        if n_bm:
+            cov = weighted_histogram()
+            r = engine.basemap_histogram(ERR_WEIGHTED, cov.edges)
+            cov.set_counts(r["counts"])
+            text = ("Base map factors\n"
+                    f"cost contrib: {r['cost']:.3e}, n. factors: {r['n_factors']}, n. failing: {r['n_failing']}  -~oOo~-  "
+                    f"histogram (covariance-weighted costs):\n{cov.show(precision=1)}")
+            hists = {"weighted": cov}
+            if show_pixel:
+                pix = pixel_histogram()
+                pix.set_counts(engine.basemap_histogram(ERR_UNWEIGHTED, pix.edges)["counts"])
+                text += f"image-reprojection error histogram (pixel distance):\n{indent(pix.show(precision=1))}\n"
+                hists["pixel"] = pix
+            sections.append(Section("visual", "Base map factors", "", (), int(r["n_factors"]), int(r["n_failing"]),
+                                    float(r["cost"]), hists, {}, text))
 
     # inertial (showHistogramsInertial, Histograms.cpp:309-442): shown when there are main inertial factors
     if engine.num_factors(F_IMU):
